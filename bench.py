@@ -2,12 +2,16 @@
 """Headline benchmark: tile-gene pairs/sec of the full Spatial-CLIP train step on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                     (+ what the last timed step computed, as DIR/*.npy)
+    python bench.py ... --full                                 (+ parity vs the fp32 oracle, per-kernel roofline passes,
+                                                                  the N > 1 communication probe, the CPU baseline)
 
-One "step" = forward (ViT image tower + gene tower) + global-batch contrastive loss + backward + gradient
-all-reduce (mean) + grad-norm clip 1.0 + AdamW + cosine-warmup scheduler step -- the reference's training_step
-plus what Lightning does after it.  Workload = BASELINE.json configs[1]/[2]: ViT-B/16 + gene-MLP
-(20000 -> 512 -> 512), local batch 256, ClipLoss over the RCCL-gathered global batch 256*N, synthetic 224x224
-tiles already resident in HBM.  Rank 0 prints ONE JSON line."""
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure or check runs
+only under --full, after the timed region. One "step" = forward (ViT image tower + gene tower) + global-batch
+contrastive loss + backward + gradient all-reduce (mean) + grad-norm clip 1.0 + AdamW + cosine-warmup scheduler step
+-- the reference's training_step plus what Lightning does after it. Workload = BASELINE.json
+configs[1]/[2]: ViT-B/16 + gene-MLP (20000 -> 512 -> 512), local batch 256, ClipLoss over the RCCL-gathered global
+batch 256*N, synthetic 224x224 tiles already resident in HBM. Rank 0 prints ONE JSON line."""
 import argparse
 import json
 import os
@@ -274,6 +278,35 @@ def spawn_ranks(n: int, argv) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+DUMP_PER_TENSOR = 65536             # elements of one parameter written whole; a larger one is sampled at this many positions
+
+
+def dump_outputs(out_dir: str, loss, state) -> dict:
+    """What the last timed step hands its caller, as float32 .npy files under ``out_dir``: ``loss.npy`` (its loss) and
+    ``param.<name>.npy`` (every parameter after its optimiser update, flattened).  A parameter larger than the per-tensor
+    share of 48 MB is sampled at sorted positions drawn by a generator seeded with 0 from its size alone: two builds, or two
+    runs with the same arguments, write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_PER_TENSOR, (48 * 2 ** 20) // 4 // max(1, len(state)))
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float32)}
+    for name, t in state.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["param." + name] = flat.float().cpu().numpy()
+    nbytes = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        nbytes += os.path.getsize(path)
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+    return {"dir": out_dir, "files": len(arrays), "bytes": nbytes, "per_tensor_sample": cap}
+
+
 def note(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(f"[bench +{time.time() - T0:.1f}s] {msg}", file=sys.stderr, flush=True)
@@ -293,6 +326,13 @@ def main():
     ap.add_argument("--model", default="ViT-B-16-gene")
     ap.add_argument("--n-genes", type=int, default=20000)
     ap.add_argument("--loss", default="clip", choices=["clip", "spatial"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: parity against the fp32 oracle at the "
+                         "initial and a trained point, the per-kernel (roofline) passes, the N > 1 communication probe and the "
+                         "CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its loss and a fixed sample of the updated "
+                         "parameters) as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--no-loss-delta", action="store_true")
@@ -308,6 +348,10 @@ def main():
     ap.add_argument("--residual-stream", default="bf16", choices=["fp32", "bf16"],
                     help="the forward residual stream of the patch towers: bf16 like the reference's autocast (default) or fp32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:               # a plain run: set-up, warm-up, the timed steps and the line, nothing else
+        args.no_cpu_baseline = args.no_kernel_events = args.no_loss_delta = args.no_comm_probe = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -475,6 +519,10 @@ def main():
     for k, v in coll.items():
         note(f"collective per step and rank: {k}: {v['launches_per_step']} launches, {v['mbytes_per_step']} MB")
     note(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step (host enqueue {t_host / args.steps * 1e3:.2f} ms/step)")
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before any --full pass below runs more steps on these weights
+        dumped = dump_outputs(args.dump_outputs, loss, n.state_dict())
+        note(f"outputs of the last timed step: {dumped}")
     # Per-kernel durations: the SAME K steps again with every GEMM launch bracketed by HIP events on its launch stream.
     # Kept out of the timed region above because the 2 x ~150 event markers per step perturb the GPU pipeline (~+10 %).
     # The weight-gradient GEMMs normally run on a side stream beside the chain, which stretches every kernel that
@@ -651,7 +699,7 @@ def main():
                "parity": None if delta_init is None else {
                    "initial_weights": delta_init, "after_training_steps": delta,
                    "within_tolerance": bool(delta_init["within_tolerance"] and delta["within_tolerance"])},
-               "roofline": roofline, "cpu_baseline": cpu}
+               "roofline": roofline, "cpu_baseline": cpu, "full": args.full, "outputs": dumped}
         sys.stdout.flush()
         os.dup2(_stdout_fd, 1)
         print(json.dumps(out), flush=True)

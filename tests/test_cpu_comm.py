@@ -102,10 +102,10 @@ def _fg_worker(rank, world, port, ret):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank),
-                       "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world)})
+                       "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world), "SC_DIST_BACKEND": "gloo"})
     import spatial_clip_amd  # noqa: F401
     from spatial_clip_amd import comm
-    assert comm.init_from_env() == (rank, rank, world)          # gloo on a CPU-only host
+    assert comm.init_from_env() == (rank, rank, world)          # gloo, also where a GPU would make RCCL the default
     assert comm.init_from_env(expect_world=world) == (rank, rank, world)   # idempotent
     try:
         comm.init_from_env(expect_world=world + 1)

@@ -297,7 +297,7 @@ def test_bench_under_torchrun_two_ranks_prints_one_line():
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
             "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py")]
     args = ["--steps", "2", "--warmup", "1", "--model", "ViT-Ti-16-gene", "--batch", "16", "--n-genes", "512",
-            "--no-cpu-baseline", "--no-loss-delta", "--no-kernel-events"]
+            "--full", "--no-cpu-baseline", "--no-loss-delta", "--no-kernel-events"]
     r = subprocess.run(base + ["--gpus", "2"] + args, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 # Every step writes under gpurun_out/<tag>/; steps are joined with && semantics (set -e): a failed or killed GPU step ends
 # the session.  Steps:
 #   tests:<files>[@<-k expression>]              pytest -m gpu on the given files (spaces written as '+')
-#   bench[:extra args]                           python bench.py --steps 20 --warmup 5 [extra]
+#   bench[:extra args]                           python bench.py --steps 20 --warmup 5 --full [extra]
 #   benchq[:extra args]                          quick bench line: no CPU baseline, no oracle, no kernel events
 #   prof[:single|side]                           rocprofv3 --kernel-trace --stats of the bench command (SC_OVERLAP=0 / default)
 #   pmc                                          the FETCH_SIZE / WRITE_SIZE / MFMA PMC passes + summaries
@@ -31,7 +31,7 @@ for STEP in "$@"; do
       else timeout -k 10 1100 python -m pytest $FILES -m gpu -x -q -s 2>&1 | tee "$LOG" | tail -40; fi ;;
     bench)  # (file name = first 40 characters of the arguments + a checksum of all of them: two long argument lists that share a prefix must not overwrite each other)
       BN="bench_$(echo "$ARG" | tr -c 'A-Za-z0-9' _ | cut -c1-40)_$(echo "$ARG" | cksum | cut -d' ' -f1)"
-      timeout -k 10 900 python bench.py --steps 20 --warmup 5 $ARG > "$OUT/$BN.json" 2> "$OUT/$BN.err" ; tail -c 400 "$OUT/$BN.json" ;;
+      timeout -k 10 900 python bench.py --steps 20 --warmup 5 --full $ARG > "$OUT/$BN.json" 2> "$OUT/$BN.err" ; tail -c 400 "$OUT/$BN.json" ;;
     benchq) timeout -k 10 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-loss-delta --no-kernel-events $ARG 2> "$OUT/benchq.err" | tee -a "$OUT/benchq.jsonl" | cut -c1-400 ;;
     prof)
       MODE=${ARG%% *}; MODE=${MODE:-single}; EXTRA=""; [[ "$ARG" == *" "* ]] && EXTRA=${ARG#* }      # prof:single+--model+X ...: extra bench.py arguments
