@@ -305,6 +305,14 @@ int sc_contrastive_loss_bwd(float* z_inout, int B, int G, const float* logit_sca
                             const float* grad_out, float* rowgrad, float* dscale, float* dbias, void* stream);
 /* RecallAtK (src/models/components/metrics.py:22-36) on the local [B,B] block of z[0]: hits3 += {R@1,R@5,R@10}. */
 int sc_recall_hits(const float* z_image_rows, int G, int B, int col0, int* hits3, void* stream);
+/* SigLipLoss (src/open_clip/loss.py:330-460) on the device.  z_inout[B][G] = local image_features . all_text^T; the
+ * positives are the diagonal of the rank's block (column col0 + i).  One pass: loss terms softplus(-y x) with
+ * x = s z + b, dz = s (dl/dx) / B written over z; rowpart[B][3] = per-row {sum loss, sum (dl/dx) z, sum dl/dx}; a
+ * fixed-order finalize writes loss_out[0], d_scale (of the *exponentiated* scale) and d_bias (each may be NULL).
+ * logit_bias NULL = no bias.  recall_hits3 (may be NULL) += R@1/5/10 of the diagonal block, counted before z is
+ * overwritten.  No float atomics: bit-identical across launches. */
+int sc_siglip_loss(float* z_inout, int B, int G, int col0, const float* logit_scale, const float* logit_bias,
+                   float* rowpart, float* loss_out, float* d_scale, float* d_bias, int* recall_hits3, void* stream);
 /* Validation-only zero-shot gene-expression metric (src/metrics/zero_shot.py:62-88): sample-wise
  * Pearson correlation of pred[rows, cols] (image_features @ gene_bank^T) against the rank-weighted targets, rows with
  * sqrt(sum pc^2) * sqrt(sum tc^2) <= 1e-6 score 0.  pcc[rows] (may be NULL); sum_count[0] += sum(pcc),

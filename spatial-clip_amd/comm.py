@@ -369,6 +369,22 @@ def _ids_view(buf: torch.Tensor, D: int, which: int) -> torch.Tensor:
     return flat.as_strided((G,), (cols // 2,), (D // 2 + which))
 
 
+def gather_rows(feat: torch.Tensor) -> torch.Tensor:
+    """Rank-major concatenation of every rank's [B, D] rows (one collective on the caller's stream): the text-only gather
+    of the sigmoid loss."""
+    if not is_dist():
+        return feat
+    _, W = world()
+    feat = feat.contiguous()
+    out = torch.empty((W * feat.shape[0], feat.shape[1]), dtype=feat.dtype, device=feat.device)
+    _count("all_gather(features|ids)", out.numel() * 4)
+    if _native is not None and feat.is_cuda and feat.dtype == torch.float32:
+        _native.all_gather(feat, out, torch.cuda.current_stream(feat.device))
+    else:
+        dist.all_gather_into_tensor(out, feat)
+    return out
+
+
 def gather_packed(image_features: torch.Tensor, text_features: torch.Tensor,
                   image_tile_ids: Optional[torch.Tensor] = None, text_tile_ids: Optional[torch.Tensor] = None):
     """Rank-major concatenation of every rank's rows: returns (all_image, all_text, all_image_ids, all_text_ids).
@@ -424,6 +440,7 @@ class FeatureGather:
         self._send, self._recv, self._done, self._src = {}, {}, {}, {}
         self._ids = (None, None)
         self.launched = 0          # number of collectives issued (tests)
+        self.skip = frozenset()    # sides the loss does not gather ("image" for the sigmoid loss)
 
     def begin(self, ids_i: Optional[torch.Tensor], ids_t: Optional[torch.Tensor]) -> None:
         self._ids = (ids_i, ids_t)
@@ -438,7 +455,7 @@ class FeatureGather:
         return t
 
     def put(self, which: str, feat: torch.Tensor) -> None:
-        if not is_dist():
+        if not is_dist() or which in self.skip:
             return
         _, W = world()
         B, D = feat.shape

@@ -6,7 +6,11 @@ Reference semantics: open_clip ClipLoss (src/open_clip/loss.py:91-155, local_los
 (src/models/components/losses.py:44-124).  Nothing here synchronises with the host.
 
 The six matrix products (two similarity matrices, four gradient products) are exact-fp32 MFMA GEMMs
-(``sc_sgemm_f32_grouped``): one launch for the forward pair, one for the backward four."""
+(``sc_sgemm_f32_grouped``): one launch for the forward pair, one for the backward four.
+
+``siglip_forward_backward``: the sigmoid loss (open_clip SigLipLoss, src/open_clip/loss.py:330-460) on the same GEMMs --
+one similarity matrix (image . all_text^T), one elementwise loss pass, two gradient products, only the text features
+gathered."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -44,7 +48,8 @@ def contrastive_forward_backward(
     (default: all B rows, diagonal at column rank*B).  ``join_local`` (single process, G == B): the gathered-feature
     terms are accumulated straight onto the direct terms by the GEMMs (``d_image`` / ``d_text`` then hold the complete
     feature gradients and no ``d_all`` is formed).  ``want_recall=False`` skips the R@k counters.
-    ``grads``: one flat fp32 buffer [2 B D + 1] = d_image | d_text | d_scale (one launch scales all three in backward)."""
+    ``grads``: one flat fp32 buffer [2 B D + 2] = d_image | d_text | d_scale | d_bias (one launch scales all four in
+    backward)."""
     f_i = _rows(image_features)
     f_t = _rows(text_features)
     a_t = f_t if all_text is None else _rows(all_text)
@@ -103,10 +108,10 @@ def contrastive_forward_backward(
             row0, nrow = recall_rows
             ops.recall_hits(z[0][row0:], G, nrow, row0, recall_hits)
     rowgrad = torch.empty((2 * B, 2), dtype=torch.float32, device=dev)
-    grads = torch.empty(2 * B * D + 1, dtype=torch.float32, device=dev)     # d_image | d_text | d_scale
+    grads = torch.empty(2 * B * D + 2, dtype=torch.float32, device=dev)     # d_image | d_text | d_scale | d_bias
     d_image, d_text = grads[:B * D].view(B, D), grads[B * D:2 * B * D].view(B, D)
-    d_scale = grads[2 * B * D:]
-    d_bias = torch.empty(1, dtype=torch.float32, device=dev)
+    d_scale = grads[2 * B * D:2 * B * D + 1]
+    d_bias = grads[2 * B * D + 1:]
     ops.contrastive_loss_bwd(z, B, G, scale, cap, bias, lab_col, lab_w, nlab, w, rowstats, loss_out, None, rowgrad,
                              d_scale, d_bias)
     direct = [(z[0], G, 1, a_t, 1, a_t.stride(0), d_image, D, B, D, G),     # dz_it . all_text        (K = G: first)
@@ -126,4 +131,51 @@ def contrastive_forward_backward(
         (z[1], 1, G, f_t, 1, f_t.stride(0), d_all[:, :D], 2 * D, G, D, B),   # dz_ti^T . text   -> d all_image
     ])
     out.update(d_all=d_all, d_all_image=d_all[:, :D], d_all_text=d_all[:, D:])
+    return out
+
+
+def siglip_forward_backward(
+        image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
+        logit_bias: Optional[torch.Tensor] = None, *, all_text: Optional[torch.Tensor] = None, rank: int = 0,
+        recall_hits: Optional[torch.Tensor] = None, join_local: bool = False) -> Dict[str, torch.Tensor]:
+    """Sigmoid loss of the local images against the (gathered) texts, forward AND backward for an upstream gradient of 1.
+
+    Rank r scores its B images against all G texts; the positives are the diagonal of its own block (columns r*B..),
+    every other pair is a negative -- the objective of every ``dist_impl`` of the reference.  ``logit_scale`` is the
+    exponentiated scale; ``logit_bias`` may be None.  Returns loss (0-d), d_image [B,D] (complete), d_scale, d_bias (of
+    the exponentiated scale / the bias), ``grads`` = one flat buffer [2 B D + 2] = d_image | d_text | d_scale | d_bias,
+    and either (``join_local``, single process, G == B) d_text = dz^T . image written into ``grads``, or
+    d_all_text [G,D] = this rank's contribution to every rank's text features (the reduce-scatter operand); d_text
+    is then left for the caller to fill."""
+    f_i = _rows(image_features)
+    f_t = _rows(text_features)
+    a_t = f_t if all_text is None else _rows(all_text)
+    dev = f_i.device
+    B, D = f_i.shape
+    G = a_t.shape[0]
+    if f_t.shape != f_i.shape or a_t.shape[1] != D:
+        raise ValueError("feature shapes disagree")
+    if (rank + 1) * B > G:
+        raise ValueError(f"rank {rank} with local batch {B} does not fit global batch {G}")
+    scale = logit_scale.detach().reshape(1).float()
+    bias = None if logit_bias is None else logit_bias.detach().reshape(1).float()
+    z = torch.empty((B, G), dtype=torch.float32, device=dev)
+    ops.sgemm_grouped([(f_i, f_i.stride(0), 1, a_t, a_t.stride(0), 1, z, G, B, G, D)])     # z = image . all_text^T
+    grads = torch.empty(2 * B * D + 2, dtype=torch.float32, device=dev)     # d_image | d_text | d_scale | d_bias
+    d_image, d_text = grads[:B * D].view(B, D), grads[B * D:2 * B * D].view(B, D)
+    d_scale, d_bias = grads[2 * B * D:2 * B * D + 1], grads[2 * B * D + 1:]
+    rowpart = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    loss_out = torch.empty(1, dtype=torch.float32, device=dev)
+    ops.siglip_loss(z, B, G, rank * B, scale, bias, rowpart, loss_out, d_scale, d_bias, recall_hits)   # z <- dz
+    out = {"loss": loss_out[0], "d_image": d_image, "d_text": d_text, "d_scale": d_scale[0], "d_bias": d_bias[0],
+           "recall_hits": recall_hits, "grads": grads}
+    direct = (z, G, 1, a_t, 1, a_t.stride(0), d_image, D, B, D, G)              # dz . all_text   -> d image
+    if join_local:
+        if G != B or rank != 0:
+            raise ValueError("join_local: only for the single-process head (G == B)")
+        ops.sgemm_grouped([direct, (z, 1, G, f_i, 1, f_i.stride(0), d_text, D, G, D, B)])   # dz^T . image -> d text
+        return out
+    d_all_text = torch.empty((G, D), dtype=torch.float32, device=dev)
+    ops.sgemm_grouped([direct, (z, 1, G, f_i, 1, f_i.stride(0), d_all_text, D, G, D, B)])  # dz^T . image -> d all_text
+    out.update(d_all_text=d_all_text)
     return out

@@ -243,6 +243,72 @@ __global__ __launch_bounds__(256) void recall_kernel(const float* __restrict__ z
     }
 }
 
+// ---------------------------------------------------------------------------------------------- sigmoid (SigLIP) loss
+// reference: src/open_clip/loss.py:358-379.  Per element of z[B][G] (cosine similarities of the local images against the
+// gathered texts): x = s*z + b, y = +1 on the rank's diagonal (j == col0 + i) else -1, loss softplus(-y*x),
+// dl/dx = -y*sigmoid(-y*x).  Elementwise, so one pass writes dz = s*(dl/dx)/B in place and the per-row partials
+// {sum loss, sum (dl/dx)*z, sum dl/dx}; a one-block finalize sums the rows in a fixed order (no float atomics).
+// Stable forms throughout: with e = exp(-|x|), softplus(t) = max(t,0) + log1p(e) and sigmoid(t) = 1/(1+e) or e/(1+e)
+// -- at b = -10 a negative contributes ~4.5e-5, which log(1 + e) in fp32 would round away.
+__global__ __launch_bounds__(256) void siglip_rows_kernel(float* __restrict__ z, int B, int G, int col0,
+                                                          const float* __restrict__ scale,
+                                                          const float* __restrict__ bias,
+                                                          float* __restrict__ rowpart) {
+    __shared__ float sm[4];
+    const int i = blockIdx.x;
+    float* zr = z + (long long)i * G;
+    const float s = *scale;
+    const float bz = bias ? *bias : 0.f;
+    const float c = s / (float)B;
+    const int diag = col0 + i;
+    float sl = 0.f, sdz = 0.f, sdl = 0.f;
+    for (int j = threadIdx.x; j < G; j += 256) {
+        const float zz = zr[j];
+        const float x = s * zz + bz;
+        const float t = j == diag ? -x : x;                 // t = -y*x
+        const float e = expf(-fabsf(x));
+        const float r = 1.0f / (1.0f + e);
+        const float sig = t >= 0.f ? r : e * r;             // sigmoid(t)
+        const float dl = j == diag ? -sig : sig;            // -y*sigmoid(-y*x)
+        sl += fmaxf(t, 0.f) + log1pf(e);
+        sdz += dl * zz;
+        sdl += dl;
+        zr[j] = c * dl;
+    }
+    sl = block_sum(sl, sm);
+    sdz = block_sum(sdz, sm);
+    sdl = block_sum(sdl, sm);
+    if (threadIdx.x == 0) {
+        float* o = rowpart + (long long)i * 3;
+        o[0] = sl;
+        o[1] = sdz;
+        o[2] = sdl;
+    }
+}
+
+// loss = sum_i rowpart[i][0] / B ; d(exp'd scale) = sum_i rowpart[i][1] / B ; d bias = sum_i rowpart[i][2] / B
+__global__ __launch_bounds__(256) void siglip_finalize_kernel(const float* __restrict__ rowpart, int B,
+                                                              float* __restrict__ loss_out, float* __restrict__ dscale,
+                                                              float* __restrict__ dbias) {
+    __shared__ float sm[4];
+    float a = 0.f, b = 0.f, c = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const float* r = rowpart + (long long)i * 3;
+        a += r[0];
+        b += r[1];
+        c += r[2];
+    }
+    a = block_sum(a, sm);
+    b = block_sum(b, sm);
+    c = block_sum(c, sm);
+    if (threadIdx.x == 0) {
+        const float inv = 1.0f / (float)B;
+        if (loss_out) *loss_out = a * inv;
+        if (dscale) *dscale = b * inv;
+        if (dbias) *dbias = c * inv;
+    }
+}
+
 __global__ void exp_scalar_kernel(const float* __restrict__ x, float* __restrict__ y) { *y = __expf(*x); }
 __global__ void exp_scalar_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
                                       float mult) {
@@ -348,6 +414,24 @@ extern "C" int sc_pcc_rows(const float* pred, long long ldp, const float* target
 extern "C" int sc_recall_hits(const float* z_image_rows, int G, int B, int col0, int* hits3, void* stream) {
     SC_CHECK(B > 0 && G >= B && col0 >= 0 && col0 + B <= G, "sc_recall_hits: bad shape");
     recall_kernel<<<B, 256, 0, (hipStream_t)stream>>>(z_image_rows, G, B, col0, hits3);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_siglip_loss(float* z_inout, int B, int G, int col0, const float* logit_scale,
+                              const float* logit_bias, float* rowpart, float* loss_out, float* dscale, float* dbias,
+                              int* recall_hits3, void* stream) {
+    SC_CHECK(B > 0 && G >= B && col0 >= 0 && (long long)col0 + B <= G, "sc_siglip_loss: bad shape B=%d G=%d col0=%d",
+             B, G, col0);
+    SC_CHECK(z_inout != nullptr && logit_scale != nullptr && rowpart != nullptr, "sc_siglip_loss: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (recall_hits3) {     // ranks of the diagonal block, read before z is overwritten with dz
+        recall_kernel<<<B, 256, 0, st>>>(z_inout, G, B, col0, recall_hits3);
+        SC_LAUNCH_CHECK();
+    }
+    siglip_rows_kernel<<<B, 256, 0, st>>>(z_inout, B, G, col0, logit_scale, logit_bias, rowpart);
+    SC_LAUNCH_CHECK();
+    siglip_finalize_kernel<<<1, 256, 0, st>>>(rowpart, B, loss_out, dscale, dbias);
     SC_LAUNCH_CHECK();
     return 0;
 }

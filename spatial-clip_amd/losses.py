@@ -12,15 +12,16 @@ from typing import Dict, Optional
 import torch
 
 from . import comm, ops
-from .contrastive import contrastive_forward_backward
+from .contrastive import contrastive_forward_backward, siglip_forward_backward
 
 
 class _ContrastiveFn(torch.autograd.Function):
-    """Forward computes the loss AND its feature / scale gradients (for an upstream gradient of 1); backward
-    scales them by the actual upstream gradient."""
+    """Forward computes the loss AND its feature / scale / bias gradients (for an upstream gradient of 1); backward
+    scales them by the actual upstream gradient.  ``logit_bias`` (may be None) is an autograd input: its gradient is
+    the d_bias the loss kernels form anyway."""
 
     @staticmethod
-    def forward(ctx, image_features, text_features, logit_scale, owner, kw):
+    def forward(ctx, image_features, text_features, logit_scale, logit_bias, owner, kw):
         rank, W = comm.world()
         dist_on = comm.is_dist()
         ids_i, ids_t = kw.get("image_tile_ids"), kw.get("text_tile_ids")
@@ -43,7 +44,7 @@ class _ContrastiveFn(torch.autograd.Function):
                       all_text_tile_ids=all_ids_t, neighbor_tile_ids=kw.get("neighbor_tile_ids"),
                       neighbor_alphas=kw.get("neighbor_alphas"), cap_logit_scale=owner.cap_logit_scale,
                       temp_reg_weight=owner.temp_reg_weight, neighbor_alpha_scale=owner.neighbor_alpha_scale,
-                      logit_bias=kw.get("logit_bias"), recall_hits=owner.recall_hits, want_recall=False)
+                      logit_bias=logit_bias, recall_hits=owner.recall_hits, want_recall=False)
         if dist_on and owner.mode == "clip" and not owner.local_loss:
             # loss.py:119-121: every rank forms the full [G,G] logits of the global batch (labels arange(G))
             if late is not None:
@@ -70,19 +71,21 @@ class _ContrastiveFn(torch.autograd.Function):
             else:           # single process: the head's GEMMs accumulated the gathered-feature terms onto the direct ones
                 d_img, d_txt = res["d_image"], res["d_text"]
         ctx.flat = res["grads"] if d_img is res["d_image"] and d_txt is res["d_text"] else None
-        ctx.save_for_backward(d_img, d_txt, res["d_scale"])
+        ctx.save_for_backward(d_img, d_txt, res["d_scale"], res["d_bias"])
         owner.last = res
         return res["loss"]
 
     @staticmethod
     def backward(ctx, g):
-        d_img, d_txt, d_s = ctx.saved_tensors
+        d_img, d_txt, d_s, d_b = ctx.saved_tensors
         g = g.detach().reshape(1).float()
-        if ctx.flat is not None and g.is_cuda:     # d_image | d_text | d_scale are one buffer: one launch applies the upstream gradient
+        want_b = ctx.needs_input_grad[3]
+        if ctx.flat is not None and g.is_cuda:     # d_image | d_text | d_scale | d_bias are one buffer: one launch applies the upstream gradient
             out = ops.scale_by_scalar(ctx.flat, g, torch.empty_like(ctx.flat))
             n = d_img.numel()
-            return out[:n].view_as(d_img), out[n:2 * n].view_as(d_txt), out[2 * n], None, None
-        return d_img * g, d_txt * g, d_s * g, None, None
+            return out[:n].view_as(d_img), out[n:2 * n].view_as(d_txt), out[2 * n], \
+                (out[2 * n + 1] if want_b else None), None, None
+        return d_img * g, d_txt * g, d_s * g, (d_b * g if want_b else None), None, None
 
 
 class _LossBase(torch.nn.Module):
@@ -129,7 +132,7 @@ class ClipLoss(_LossBase):
 
     def forward(self, image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
                 logit_bias: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        loss = _ContrastiveFn.apply(image_features, text_features, logit_scale, self, {"logit_bias": logit_bias})
+        loss = _ContrastiveFn.apply(image_features, text_features, logit_scale, logit_bias, self, {})
         return {"contrastive_loss": loss}
 
 
@@ -153,6 +156,73 @@ class SpatialLoss(_LossBase):
                 neighbor_alphas: torch.Tensor, logit_bias: Optional[torch.Tensor] = None,
                 output_dict: bool = True) -> Dict[str, torch.Tensor]:
         kw = {"image_tile_ids": image_tile_ids, "text_tile_ids": text_tile_ids,
-              "neighbor_tile_ids": neighbor_tile_ids, "neighbor_alphas": neighbor_alphas, "logit_bias": logit_bias}
-        loss = _ContrastiveFn.apply(image_features, text_features, logit_scale, self, kw)
+              "neighbor_tile_ids": neighbor_tile_ids, "neighbor_alphas": neighbor_alphas}
+        loss = _ContrastiveFn.apply(image_features, text_features, logit_scale, logit_bias, self, kw)
         return {"contrastive_loss": loss}
+
+
+class _SigLipFn(torch.autograd.Function):
+    """Sigmoid loss forward AND its feature / scale / bias gradients (upstream gradient 1); backward scales them."""
+
+    @staticmethod
+    def forward(ctx, image_features, text_features, logit_scale, logit_bias, owner):
+        rank, W = comm.world()
+        dist_on = comm.is_dist()
+        img = image_features.detach().contiguous().float()
+        txt = text_features.detach().contiguous().float()
+        B, D = img.shape
+        all_t = None
+        if dist_on:
+            fg = owner.prefetched
+            if fg is not None and fg.has("text", txt):
+                all_t = fg.take("text")[0]       # launched from inside the net's forward, under the vision tower
+            else:
+                all_t = comm.gather_rows(txt)
+        res = siglip_forward_backward(img, txt, logit_scale.detach(), logit_bias, all_text=all_t,
+                                      rank=rank if dist_on else 0, recall_hits=owner.recall_hits,
+                                      join_local=not dist_on)
+        if dist_on:
+            # autograd of the text exchange (neighbour_exchange_*_with_grad / all_gather): every rank's d all_text summed
+            # onto the owner's rows -- the image features are never gathered, so they have only the direct term
+            res["d_text"].copy_(comm.reduce_scatter_sum(res["d_all_text"]))
+        ctx.flat = res["grads"]
+        ctx.B, ctx.D = B, D
+        owner.last = res
+        return res["loss"]
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.detach().reshape(1).float()
+        flat = ctx.flat
+        out = ops.scale_by_scalar(flat, g, torch.empty_like(flat)) if g.is_cuda else flat * g
+        n = ctx.B * ctx.D
+        d_b = out[2 * n + 1] if ctx.needs_input_grad[3] else None
+        return out[:n].view(ctx.B, ctx.D), out[n:2 * n].view(ctx.B, ctx.D), out[2 * n], d_b, None
+
+
+class SigLipLoss(_LossBase):
+    """``SigLipLoss(cache_labels, rank, world_size, dist_impl)`` (open_clip, src/open_clip/loss.py:330-460): sigmoid
+    loss of the local images against the global batch of texts, positives on the rank's own diagonal block.
+    ``forward(image_features, text_features, logit_scale, logit_bias, output_dict=False)`` returns the 0-d loss, or
+    ``{"contrastive_loss": loss}`` with ``output_dict=True``.
+
+    Distributed: every ``dist_impl`` of the reference (bidir / shift neighbour exchange, reduce, gather) computes the
+    same objective -- rank r scores its B images against all G texts, with gradients flowing back to the remote text
+    features.  Here it is formed once for all four: one all-gather of the text features (launched under the vision
+    tower; the image features are not gathered) and one [G, D] reduce-scatter of the remote text gradients.
+    ``dist_impl`` therefore changes only the summation order relative to the reference.  Rank / world size are read
+    from the live process group at call time, like the other losses here."""
+    skip_gather = ("image",)
+
+    def __init__(self, cache_labels: bool = False, rank: int = 0, world_size: int = 1,
+                 dist_impl: Optional[str] = None):
+        super().__init__()
+        self._init_common(False, True, rank, world_size, False)
+        self.cache_labels = cache_labels
+        self.dist_impl = dist_impl or "bidir"
+        assert self.dist_impl in ("bidir", "shift", "reduce", "gather")
+
+    def forward(self, image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
+                logit_bias: Optional[torch.Tensor] = None, output_dict: bool = False):
+        loss = _SigLipFn.apply(image_features, text_features, logit_scale, logit_bias, self)
+        return {"contrastive_loss": loss} if output_dict else loss

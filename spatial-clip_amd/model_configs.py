@@ -78,6 +78,9 @@ class ModelCfg:
     # (src/open_clip/model.py:142-145,228; the OpenAI-pretrained weights were trained with it).  The gene towers are this
     # build's own definition and keep the exact-erf GELU.
     quick_gelu: bool = False
+    # SigLIP's learnable logit bias (src/open_clip/model.py:299-302; the training entry sets -10 with --siglip,
+    # main.py:225-227).  None (the default): no bias parameter at all -- parameters, flat layout and state_dict keys as before.
+    init_logit_bias: Optional[float] = None
 
 
 def _clip(embed, v_layers, v_width, patch, t_width, t_heads, t_layers=12, image=224) -> ModelCfg:

@@ -104,6 +104,7 @@ class SpatialClipLitModule(torch.nn.Module):
             if fg is None:
                 fg = self._feature_gather = comm.FeatureGather(self.device)
             want_ids = "image_tile_ids" in self._loss_fn_arg_names
+            fg.skip = frozenset(getattr(self.loss_fn, "skip_gather", ()))
             fg.begin(batch.get("image_tile_ids") if want_ids else None, batch.get("text_tile_ids") if want_ids else None)
         self.net.feature_gather = fg
         if hasattr(self.loss_fn, "prefetched"):
@@ -120,7 +121,8 @@ class SpatialClipLitModule(torch.nn.Module):
         if fused_hits:
             metrics.add_hits(features["image_features"].shape[0])
             self.loss_fn.recall_hits = None
-        return StepOutput({"loss": loss_dict["contrastive_loss"], "image_features": features["image_features"],
+        loss = loss_dict if isinstance(loss_dict, torch.Tensor) else loss_dict["contrastive_loss"]   # SigLipLoss: bare 0-d
+        return StepOutput({"loss": loss, "image_features": features["image_features"],
                            "text_features": features["text_features"], "logit_scale": features["logit_scale"]})
 
     @staticmethod

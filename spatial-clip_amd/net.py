@@ -2,8 +2,8 @@
 
 Mirror of ``src/models/components/spatial_clip_net.py:12-53`` (ctor kwargs ``model_name, pretrained, aug_cfg,
 cache_dir``; attributes ``model``, ``preprocess_train``, ``preprocess_val``, ``tokenizer``; ``forward(images,
-texts) -> {"image_features","text_features","logit_scale","logit_bias"}``).  The ``texts`` slot carries the float
-gene matrix [B, n_genes] for ``*-gene`` models.
+texts) -> {"image_features","text_features","logit_scale","logit_bias"}``; ``logit_bias`` is None unless the net is
+built with ``init_logit_bias``).  The ``texts`` slot carries the float gene matrix [B, n_genes] for ``*-gene`` models.
 
 Autograd bridge: the whole net is ONE autograd node.  Its backward runs the hand-written backward kernel sequence
 and writes parameter gradients directly into the flat gradient buffer (``p.grad`` are views of it), so the usual
@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import is_dataclass
+from dataclasses import is_dataclass, replace
 from typing import Any, Callable, Dict, List, Optional
 
 import torch
@@ -61,18 +61,21 @@ class _NetFn(torch.autograd.Function):
             if fg is not None:
                 fg.put("image", img)
         s = torch.empty(1, dtype=torch.float32, device=img.device)
-        net.store.wait_names(["logit_scale"])
+        has_bias = net.has_logit_bias
+        net.store.wait_names(["logit_scale", "logit_bias"] if has_bias else ["logit_scale"])
         ops.exp_scalar(net.store.p("logit_scale").view(1), s)
         net._scale = s
         # Return ALIASES, not the tensors the towers keep (tower.f): autograd stamps this node as grad_fn on the objects
         # returned here, and a tensor that the net holds AND that points back at a node holding the net (ctx.net) is a
         # reference cycle through C++ that Python's collector cannot see -- every net ever built would keep its HBM.
+        if has_bias:        # the bias parameter itself (an alias): its gradient comes back through this node
+            return img.detach(), txt.detach(), s.view(()), net.store.p("logit_bias").detach()
         return img.detach(), txt.detach(), s.view(())
 
     @staticmethod
-    def backward(ctx, d_img, d_txt, d_s):
+    def backward(ctx, d_img, d_txt, d_s, d_b=None):
         ctx.net.store.wait_all()      # an optimiser update running behind the forward reads the gradients this backward overwrites
-        ctx.net._backward(d_img, d_txt, d_s)
+        ctx.net._backward(d_img, d_txt, d_s, d_b)
         return None, None, None, None
 
 
@@ -178,7 +181,14 @@ class _ClipFacade:
         st.wait_names(["logit_scale"])      # an update may still be running behind the forward (communication stream)
         return st.params["logit_scale"]
 
-    logit_bias = None
+    @property
+    def logit_bias(self) -> Optional[torch.nn.Parameter]:
+        """The learnable bias of a net built with ``init_logit_bias`` (src/open_clip/model.py:299-302), else None."""
+        st = self._net.store
+        if "logit_bias" not in st.params:
+            return None
+        st.wait_names(["logit_bias"])
+        return st.params["logit_bias"]
 
     def encode_image(self, image: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         """CLIP.encode_image (src/open_clip/model.py:326-328), inference only: ``normalize=False`` returns the
@@ -207,7 +217,8 @@ class SpatialClipNet(torch.nn.Module):
                  cache_dir: Optional[str] = None, n_genes: Optional[int] = None, gene_hidden: Optional[int] = None,
                  device: Optional[str] = None, seed: int = 0, model_cfg: Optional[ModelCfg] = None,
                  tokenizer_vocab: Optional[str] = None, precision: str = "bf16", grad_checkpointing: bool = False,
-                 residual_stream: str = "bf16"):
+                 residual_stream: str = "bf16", init_logit_scale: Optional[float] = None,
+                 init_logit_bias: Optional[float] = None):
         super().__init__()
         if aug_cfg is not None and not isinstance(aug_cfg, (dict, AugmentationCfg)) and not is_dataclass(aug_cfg) \
                 and not hasattr(aug_cfg, "items"):
@@ -217,6 +228,10 @@ class SpatialClipNet(torch.nn.Module):
             raise RuntimeError("SpatialClipNet needs an MI355X (HIP device): this build has no CPU fallback")
         self.device_ = torch.device(device or f"cuda:{torch.cuda.current_device()}")
         self.cfg: ModelCfg = model_cfg if model_cfg is not None else get_model_config(model_name, n_genes, gene_hidden)
+        if init_logit_scale is not None or init_logit_bias is not None:
+            # open_clip's create_model kwargs (main.py:225-227 for --siglip: log(10) and -10) override the model config
+            self.cfg = replace(self.cfg, **{k: float(v) for k, v in (("init_logit_scale", init_logit_scale),
+                                                                      ("init_logit_bias", init_logit_bias)) if v is not None})
         if self.cfg.gene is None and self.cfg.text is None:
             raise ValueError(f"{model_name}: the model config has neither a text tower nor a gene tower")
         self.model_name = model_name
@@ -241,6 +256,8 @@ class SpatialClipNet(torch.nn.Module):
         self._bpe = None
         self.grad_bucket_hook: Optional[Callable[[int, int], None]] = None
         self.feature_gather = None          # comm.FeatureGather, installed per step by the module when W > 1
+        # resident 1.0: the bias gradient is written by one in-tree launch (scale_by_scalar), no ATen kernel in the step
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device_) if self.has_logit_bias else None
         if pretrained:
             self._load_pretrained(pretrained)
         if grad_checkpointing:              # config key model.net.grad_checkpointing (open_clip: --grad-checkpointing)
@@ -358,9 +375,7 @@ class SpatialClipNet(torch.nn.Module):
             resize_pos_embed(sd, (g, g))
         if self.cfg.text is not None:           # factory.py:221: the text positions follow the model's context length
             resize_text_pos_embed(sd, self.cfg.text.context_length, model_width=self.cfg.text.width)
-        ls = sd.get("logit_scale")              # factory.py:203-204: scalar vs 1-element parameter
-        if ls is not None and ls.ndim != 0 and ls.numel() == 1:
-            sd["logit_scale"] = ls.reshape(())
+        self._fix_scalar_keys(sd)
         matched = {k: v for k, v in sd.items() if k in self.store.by_name}
         missing = [n for n in self.store.by_name if n not in matched]
         unexpected = [k for k in sd if k not in self.store.by_name]
@@ -395,15 +410,33 @@ class SpatialClipNet(torch.nn.Module):
         self.store.wait_all()
         return super().named_parameters(*a, **k)
 
+    def _fix_scalar_keys(self, sd: Dict[str, Any]) -> None:
+        """factory.py:203-213: a 1-element logit_scale / logit_bias becomes a scalar; a checkpoint without a bias loaded
+        into a net that has one (SigLIP fine-tuning from a CLIP checkpoint) gets a bias of 0.  In place."""
+        for k in ("logit_scale", "logit_bias"):
+            v = sd.get(k)
+            if v is not None and v.ndim != 0 and v.numel() == 1:
+                sd[k] = v.reshape(())
+        if self.has_logit_bias and "logit_bias" not in sd:
+            sd["logit_bias"] = torch.zeros(())
+
+    @property
+    def has_logit_bias(self) -> bool:
+        return "logit_bias" in self.store.by_name
+
     def load_state_dict(self, sd, strict: bool = True):
+        sd = dict(sd)
+        self._fix_scalar_keys(sd)
         self.store.load_state_dict(sd, strict=strict)
         self.reset_fp8_scaling()
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, images: torch.Tensor, texts: torch.Tensor) -> Dict[str, torch.Tensor]:
         self._mark_pass(torch.is_grad_enabled())    # read HERE: inside autograd.Function.forward grad mode is always off
-        img, txt, s = _NetFn.apply(self.store.params["logit_scale"], self, images, texts)
-        return {"image_features": img, "text_features": txt, "logit_scale": s, "logit_bias": None}
+        out = _NetFn.apply(self.store.params["logit_scale"], self, images, texts)
+        img, txt, s = out[:3]
+        return {"image_features": img, "text_features": txt, "logit_scale": s,
+                "logit_bias": out[3] if len(out) > 3 else None}
 
     def _mark_pass(self, train_pass: bool) -> None:
         """Tell the stacks whether the forward about to run will be differentiated.  Only such a pass records e4m3 maxima,
@@ -417,14 +450,21 @@ class SpatialClipNet(torch.nn.Module):
         if self.grad_bucket_hook is not None:
             self.grad_bucket_hook(*self.store.grad_range(names))
 
-    def _backward(self, d_img, d_txt, d_s) -> None:
+    def _backward(self, d_img, d_txt, d_s, d_b=None) -> None:
         s = self.store
         dev = self.device_
         if d_s is None:
             s.g("logit_scale").zero_()
         else:
             ops.exp_scalar_bwd(self._scale, d_s.reshape(1).float().contiguous(), s.g("logit_scale").view(1), 1.0)
-        self._bucket(["logit_scale"])
+        if self.has_logit_bias:
+            if d_b is None:
+                s.g("logit_bias").zero_()
+            else:
+                ops.scale_by_scalar(self._one, d_b.reshape(1).float().contiguous(), s.g("logit_bias").view(1))
+            self._bucket(["logit_scale", "logit_bias"])
+        else:
+            self._bucket(["logit_scale"])
         B, D = self.second.f.shape
         if d_txt is None:
             d_txt = torch.zeros((B, D), dtype=torch.float32, device=dev)

@@ -491,6 +491,12 @@ def recall_hits(z_img_rows, G, B, col0, hits3):
     check(_lib.lib().sc_recall_hits(z_img_rows.data_ptr(), G, B, col0, hits3.data_ptr(), _stream()), "sc_recall_hits")
 
 
+def siglip_loss(z, B, G, col0, scale, bias, rowpart, loss_out, dscale, dbias, hits3=None):
+    check(_lib.lib().sc_siglip_loss(z.data_ptr(), B, G, col0, scale.data_ptr(), _ptr(bias), rowpart.data_ptr(),
+                                    _ptr(loss_out), _ptr(dscale), _ptr(dbias), _ptr(hits3), _stream()),
+          "sc_siglip_loss")
+
+
 def exp_scalar(x, y):
     check(_lib.lib().sc_exp_scalar(x.data_ptr(), y.data_ptr(), _stream()), "sc_exp_scalar")
     return y

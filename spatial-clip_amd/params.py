@@ -124,6 +124,8 @@ def build_specs(cfg: ModelCfg) -> List[ParamSpec]:
         specs.append(ParamSpec("gene.fc2.weight", (cfg.embed_dim, g.hidden), f"uniform:{1.0 / math.sqrt(g.hidden)}"))
         specs.append(ParamSpec("gene.fc2.bias", (cfg.embed_dim,), f"uniform:{1.0 / math.sqrt(g.hidden)}"))
     specs.append(ParamSpec("logit_scale", (), f"const:{cfg.init_logit_scale}"))
+    if cfg.init_logit_bias is not None:          # model.py:299-302: only a model built with init_logit_bias owns one
+        specs.append(ParamSpec("logit_bias", (), f"const:{cfg.init_logit_bias}"))
     off = 0
     for s in specs:
         s.offset = off
