@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_bwd_cls_kernel(const bf16* __restric
 // returns 1 if this kernel took the launch, 0 if the shape is outside its range (caller falls back)
 int sc_attn_bwd_cls(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
                     int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (Lq != 1 || L < 2 || L > MAXL || (dh != 64 && dh != 32)) return 0;
+    if (Lq != 1 || L < 2 || (dh != 64 && dh != 32)) return 0;     // streams the keys: no bound on L
     const float scale = 1.0f / sqrtf((float)dh);
     if (dh == 64)
         attn_bwd_cls_kernel<64><<<B * H, 256, 0, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,

@@ -92,19 +92,26 @@ _REGISTRY: Dict[str, ModelCfg] = {
     "ViT-B-16": _clip(512, 12, 768, 16, 512, 8),
     "ViT-B-32": _clip(512, 12, 768, 32, 512, 8),
     "ViT-L-14": _clip(768, 24, 1024, 14, 768, 12),
+    # src/open_clip/model_configs/ViT-L-14-336.json, ViT-L-14-280.json: ViT-L/14 at 336 px (577 tokens; OpenAI's 336-px
+    # weights) and 280 px (401 tokens); above 320 tokens attention takes the long-sequence kernels
+    "ViT-L-14-336": _clip(768, 24, 1024, 14, 768, 12, image=336),
+    "ViT-L-14-280": _clip(768, 24, 1024, 14, 768, 12, image=280),
     "ViT-S-16": _clip(384, 12, 384, 16, 384, 6),
     "ViT-S-32": _clip(384, 12, 384, 32, 384, 6),
     "ViT-Ti-16": _clip(512, 12, 192, 16, 256, 4),
 }
-# src/open_clip/model_configs/ViT-B-16-quickgelu.json, ViT-B-32-quickgelu.json, ViT-L-14-quickgelu.json: the same
-# architectures with `"quick_gelu": true`
-for _base in ("ViT-B-16", "ViT-B-32", "ViT-L-14"):
+# src/open_clip/model_configs/ViT-B-16-quickgelu.json, ViT-B-32-quickgelu.json, ViT-L-14-quickgelu.json,
+# ViT-L-14-336-quickgelu.json: the same architectures with `"quick_gelu": true`
+for _base in ("ViT-B-16", "ViT-B-32", "ViT-L-14", "ViT-L-14-336"):
     _REGISTRY[_base + "-quickgelu"] = replace(_REGISTRY[_base], quick_gelu=True)
 
 
-def get_model_config(model_name: str, n_genes: Optional[int] = None, gene_hidden: Optional[int] = None) -> ModelCfg:
+def get_model_config(model_name: str, n_genes: Optional[int] = None, gene_hidden: Optional[int] = None,
+                     image_size: Optional[int] = None) -> ModelCfg:
     """``ViT-B-16`` -> reference architecture (vision + CLIP text tower); ``ViT-B-16-gene`` -> gene-MLP tower;
-    ``ViT-L-14-genetr`` -> 6-layer gene transformer tower (BASELINE configs[4])."""
+    ``ViT-L-14-genetr`` -> 6-layer gene transformer tower (BASELINE configs[4]).  ``image_size`` overrides the vision
+    tower's input size (the reference's ``create_model(force_image_size=...)``, src/open_clip/factory.py:438-439); it must
+    be a multiple of the patch size.  None keeps the config's own size."""
     name = model_name
     gene = False
     kind = "mlp"
@@ -118,10 +125,21 @@ def get_model_config(model_name: str, n_genes: Optional[int] = None, gene_hidden
     cfg = _REGISTRY[name]
     cfg = ModelCfg(cfg.embed_dim, replace(cfg.vision), replace(cfg.text) if cfg.text else None, None,
                    cfg.init_logit_scale, cfg.quick_gelu)
+    if image_size is not None:
+        cfg = with_image_size(cfg, image_size)
     if gene:
         cfg.text = None
         cfg.gene = GeneCfg(n_genes or 20000, gene_hidden or 512, kind=kind)
     return cfg
+
+
+def with_image_size(cfg: ModelCfg, image_size: int) -> ModelCfg:
+    """A copy of ``cfg`` whose vision tower takes ``image_size`` px (a positive multiple of the patch size, else
+    ValueError): (image_size / patch)^2 + 1 tokens, the positions resized on checkpoint load."""
+    size = int(image_size)
+    if size != image_size or size <= 0 or size % cfg.vision.patch_size:
+        raise ValueError(f"image_size {image_size} is not a positive multiple of the patch size {cfg.vision.patch_size}")
+    return replace(cfg, vision=replace(cfg.vision, image_size=size))
 
 
 def list_models():

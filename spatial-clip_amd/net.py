@@ -19,7 +19,7 @@ from typing import Any, Callable, Dict, List, Optional
 import torch
 
 from . import ops, streams
-from .model_configs import ModelCfg, get_model_config
+from .model_configs import ModelCfg, get_model_config, with_image_size
 from .params import ParamStore
 from .towers import GeneTower, GeneTransformerTower, TextTower, VisionTower
 
@@ -218,7 +218,7 @@ class SpatialClipNet(torch.nn.Module):
                  device: Optional[str] = None, seed: int = 0, model_cfg: Optional[ModelCfg] = None,
                  tokenizer_vocab: Optional[str] = None, precision: str = "bf16", grad_checkpointing: bool = False,
                  residual_stream: str = "bf16", init_logit_scale: Optional[float] = None,
-                 init_logit_bias: Optional[float] = None):
+                 init_logit_bias: Optional[float] = None, force_image_size: Optional[int] = None):
         super().__init__()
         if aug_cfg is not None and not isinstance(aug_cfg, (dict, AugmentationCfg)) and not is_dataclass(aug_cfg) \
                 and not hasattr(aug_cfg, "items"):
@@ -232,6 +232,10 @@ class SpatialClipNet(torch.nn.Module):
             # open_clip's create_model kwargs (main.py:225-227 for --siglip: log(10) and -10) override the model config
             self.cfg = replace(self.cfg, **{k: float(v) for k, v in (("init_logit_scale", init_logit_scale),
                                                                       ("init_logit_bias", init_logit_bias)) if v is not None})
+        if force_image_size is not None:
+            # open_clip's create_model(force_image_size=...) (src/open_clip/factory.py:438-439): the vision tower's input
+            # size, and with it the token count; a checkpoint's positions are resized to it on load
+            self.cfg = with_image_size(self.cfg, force_image_size)
         if self.cfg.gene is None and self.cfg.text is None:
             raise ValueError(f"{model_name}: the model config has neither a text tower nor a gene tower")
         self.model_name = model_name
