@@ -158,14 +158,16 @@ int sc_layernorm_bwd_x16(const void* dy, long long lddy, const void* x_bf16, lon
  * columns h*dh): softmax(q k^T / sqrt(dh)) v, fp32 softmax, optional causal mask.  Replaces
  * nn.MultiheadAttention's SDPA core (src/open_clip/transformer.py:272-287; mask :1080-1086).
  * out[B*L, H*dh] bf16, lse[B,H,L] fp32 (log-sum-exp of the scaled scores, kept for backward).
- * sc_attn_bwd writes dqkv[B*L, 3*H*dh] (bf16) and uses delta[B,H,L] as scratch.  L <= 320: dh in {32, 64}, causal or
- * not.  L > 320 (ViT-L/14 at 336 px: 577 tokens): dh = 64 and non-causal only, any L; other shapes return an error and
- * launch nothing.  SC_ATTN_LONG=1 sends dh = 64 non-causal calls of any L to the long-sequence kernels.
+ * sc_attn_bwd writes dqkv[B*L, 3*H*dh] (bf16) and uses delta[B,H,L] as scratch.  L <= 320: dh in {32, 64, 80}, causal or
+ * not (dh = 80: ViT-H, width 1280 = 16 heads; scale 1/sqrt(80); its own streamed kernels, no switches).  L > 320 (ViT-L/14
+ * at 336 px: 577 tokens): dh = 64 and non-causal only, any L; other shapes (dh = 80 above 320 tokens, every other head
+ * dim) return an error that names the limit and launch nothing.  SC_ATTN_LONG=1 sends dh = 64 non-causal calls of any L to
+ * the long-sequence kernels.
  * q_rows > 0 restricts the work to the first q_rows query positions of every sequence (the last ViT block only
  * feeds the CLS token downstream): outputs of the other rows are not written, dk / dv receive only those queries'
  * contributions; dout / out of the unused rows may hold any FINITE values (they meet exact zeros only).  dq of the
  * other rows: q_rows == 1 writes exact zeros (the caller needs no memset of dqkv); 1 < q_rows < L leaves them untouched
- * at L <= 320 and writes exact zeros on the long-sequence path. */
+ * at L <= 320 with dh 32 / 64 and writes exact zeros on the long-sequence path and at dh = 80. */
 int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dh, int causal, int q_rows,
                 void* stream);
 int sc_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -502,21 +502,21 @@ static bool attn_long(int B, int L, int H, int dh, int causal) {
 
 static int attn_check_long(const char* who, int L, int dh, int causal) {
     SC_CHECK(L <= MAXL || (dh == 64 && !causal),
-             "%s: above %d tokens only non-causal attention with head dim 64 is supported (L=%d, dh=%d, causal=%d)", who,
-             MAXL, L, dh, causal);
+             "%s: above %d tokens only non-causal attention with head dim 64 is supported; head dims 32 / 64 / 80, causal or "
+             "not, up to %d tokens (L=%d, dh=%d, causal=%d)", who, MAXL, MAXL, L, dh, causal);
     return 0;
 }
 
 // a launch on a null operand would fault the device: refused before anything is enqueued
 static int attn_check_ptrs(const char* who, bool ok, int L) {
-    SC_CHECK(ok, "%s: null operand pointer (supported: 0 < L <= %d with dh 32 / 64, causal or not; any L with dh 64, "
+    SC_CHECK(ok, "%s: null operand pointer (supported: 0 < L <= %d with dh 32 / 64 / 80, causal or not; any L with dh 64, "
                  "non-causal; got L=%d)", who, MAXL, L);
     return 0;
 }
 
 static int attn_check(const char* who, int B, int L, int H, int dh) {
     SC_CHECK(B > 0 && H > 0 && L > 0 && L <= MAXL, "%s: need 0 < L <= %d (L=%d), B=%d H=%d", who, MAXL, L, B, H);
-    SC_CHECK(dh == 64 || dh == 32, "%s: head dim must be 32 or 64 (got %d)", who, dh);
+    SC_CHECK(dh == 64 || dh == 32 || dh == 80, "%s: head dim must be 32, 64 or 80 (got %d)", who, dh);
     return 0;
 }
 
@@ -534,6 +534,13 @@ extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L,
     if (attn_check("sc_attn_fwd", B, L, H, dh)) return -1;
     const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
     hipStream_t st = (hipStream_t)stream;
+    if (dh == 80) {                                              // sc_attention_d80.hip: its own kernels, no switches
+        if (attn_check_ptrs("sc_attn_fwd", qkv && out && lse, L)) return -1;
+        SC_CHECK(sc_attn_fwd_d80(qkv, out, lse, B, L, Lq, H, dh, causal, st), "sc_attn_fwd: grid too large (B=%d L=%d H=%d)",
+                 B, L, H);
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
     const char* pe = getenv("SC_ATTN_PERSIST");                  // read per call, like SC_ATTN_BWD1 / SC_ATTN_BWD2
     const bool persist_on = !(pe && pe[0] == '0');
     if (persist_on && sc_attn_fwd_persistent(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
@@ -571,6 +578,14 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
     if (attn_check("sc_attn_bwd", B, L, H, dh)) return -1;
     const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
     hipStream_t st = (hipStream_t)stream;
+    if (dh == 80) {                                              // sc_attention_d80.hip; q_rows == 1 on the class-token kernel
+        if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
+        if (!sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st))
+            SC_CHECK(sc_attn_bwd_d80(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
+                     "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
     const int Lp = (L + 31) & ~31;
     const float scale = 1.0f / sqrtf((float)dh);
     if (sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {      // q_rows == 1

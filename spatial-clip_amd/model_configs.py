@@ -83,8 +83,8 @@ class ModelCfg:
     init_logit_bias: Optional[float] = None
 
 
-def _clip(embed, v_layers, v_width, patch, t_width, t_heads, t_layers=12, image=224) -> ModelCfg:
-    return ModelCfg(embed_dim=embed, vision=VisionCfg(image, patch, v_width, v_layers),
+def _clip(embed, v_layers, v_width, patch, t_width, t_heads, t_layers=12, image=224, head_width=64) -> ModelCfg:
+    return ModelCfg(embed_dim=embed, vision=VisionCfg(image, patch, v_width, v_layers, head_width),
                     text=TextCfg(77, 49408, t_width, t_heads, t_layers))
 
 
@@ -99,10 +99,14 @@ _REGISTRY: Dict[str, ModelCfg] = {
     "ViT-S-16": _clip(384, 12, 384, 16, 384, 6),
     "ViT-S-32": _clip(384, 12, 384, 32, 384, 6),
     "ViT-Ti-16": _clip(512, 12, 192, 16, 256, 4),
+    # src/open_clip/model_configs/ViT-H-14.json, ViT-H-16.json: width 1280 = 16 heads of 80 (sc_attention_d80.hip), 32
+    # layers, 257 / 197 tokens; text tower 1024 wide, 16 heads of 64, 24 layers
+    "ViT-H-14": _clip(1024, 32, 1280, 14, 1024, 16, t_layers=24, head_width=80),
+    "ViT-H-16": _clip(1024, 32, 1280, 16, 1024, 16, t_layers=24, head_width=80),
 }
 # src/open_clip/model_configs/ViT-B-16-quickgelu.json, ViT-B-32-quickgelu.json, ViT-L-14-quickgelu.json,
-# ViT-L-14-336-quickgelu.json: the same architectures with `"quick_gelu": true`
-for _base in ("ViT-B-16", "ViT-B-32", "ViT-L-14", "ViT-L-14-336"):
+# ViT-L-14-336-quickgelu.json, ViT-H-14-quickgelu.json: the same architectures with `"quick_gelu": true`
+for _base in ("ViT-B-16", "ViT-B-32", "ViT-L-14", "ViT-L-14-336", "ViT-H-14"):
     _REGISTRY[_base + "-quickgelu"] = replace(_REGISTRY[_base], quick_gelu=True)
 
 
@@ -140,6 +144,31 @@ def with_image_size(cfg: ModelCfg, image_size: int) -> ModelCfg:
     if size != image_size or size <= 0 or size % cfg.vision.patch_size:
         raise ValueError(f"image_size {image_size} is not a positive multiple of the patch size {cfg.vision.patch_size}")
     return replace(cfg, vision=replace(cfg.vision, image_size=size))
+
+
+# what the attention kernels take (csrc/sc_attention*.hip): head dims 32 / 64 / 80 up to 320 tokens, causal or not; above
+# that only head dim 64, non-causal
+ATTN_HEAD_DIMS = (32, 64, 80)
+ATTN_MAX_TOKENS = 320
+
+
+def check_attention_support(cfg: ModelCfg) -> None:
+    """ValueError, naming the supported head dims and lengths, if a tower of ``cfg`` has a (head dim, token count) that no
+    attention kernel takes -- raised when the net is constructed, not at its first forward."""
+    towers = [("vision", cfg.vision.width, cfg.vision.head_width, cfg.vision.tokens, False)]
+    if cfg.text is not None:
+        towers.append(("text", cfg.text.width, cfg.text.width // max(cfg.text.heads, 1), cfg.text.context_length, True))
+    if cfg.gene is not None and cfg.gene.kind == "transformer":
+        towers.append(("gene", cfg.gene.width, cfg.gene.head_width, cfg.gene.tokens, False))
+    for tower, width, dh, tokens, causal in towers:
+        if dh <= 0 or width % dh:
+            raise ValueError(f"{tower} tower: width {width} is not a multiple of the head dim {dh}")
+        ok = (dh in ATTN_HEAD_DIMS and tokens <= ATTN_MAX_TOKENS) or (dh == 64 and not causal)
+        if not ok:
+            raise ValueError(
+                f"{tower} tower: no attention kernel for head dim {dh} at {tokens} tokens"
+                f"{' (causal)' if causal else ''}; supported: head dims {' / '.join(map(str, ATTN_HEAD_DIMS))} up to "
+                f"{ATTN_MAX_TOKENS} tokens, and head dim 64 (non-causal) at any length")
 
 
 def list_models():

@@ -19,7 +19,7 @@ from typing import Any, Callable, Dict, List, Optional
 import torch
 
 from . import ops, streams
-from .model_configs import ModelCfg, get_model_config, with_image_size
+from .model_configs import ModelCfg, check_attention_support, get_model_config, with_image_size
 from .params import ParamStore
 from .towers import GeneTower, GeneTransformerTower, TextTower, VisionTower
 
@@ -238,6 +238,7 @@ class SpatialClipNet(torch.nn.Module):
             self.cfg = with_image_size(self.cfg, force_image_size)
         if self.cfg.gene is None and self.cfg.text is None:
             raise ValueError(f"{model_name}: the model config has neither a text tower nor a gene tower")
+        check_attention_support(self.cfg)       # e.g. ViT-H-14 at 378 px: head dim 80 has no kernel above 320 tokens
         self.model_name = model_name
         if precision not in ("bf16", "bf16-mixed", "fp8", "fp8-mixed"):
             raise ValueError(f"precision {precision!r}: 'bf16' / 'bf16-mixed' (the reference's bf16-mixed policy) or "

@@ -172,6 +172,10 @@ def workspace(nfloat: int, device, tag: str = "ws", dtype=torch.float32) -> torc
 # ------------------------------------------------------------------------------------------ attention
 def attn_fwd(qkv: torch.Tensor, B: int, L: int, H: int, dh: int, causal: bool = False,
              out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, q_rows: int = 0):
+    """softmax(q k^T / sqrt(dh)) v on the packed bf16 ``qkv`` [B*L, 3*H*dh]: (out bf16 [B*L, H*dh], lse fp32 [B, H, L]).
+    Head dims 32 / 64 / 80 up to 320 tokens, causal or not (80: ViT-H, sc_attention_d80.hip); head dim 64 non-causal at any
+    length.  Anything else raises RuntimeError naming the limit, before a launch.  ``q_rows`` > 0: only the first ``q_rows``
+    query rows of every sequence are computed."""
     _req(qkv, torch.bfloat16, "qkv")
     if out is None:
         out = torch.empty((B * L, H * dh), dtype=torch.bfloat16, device=qkv.device)
@@ -184,6 +188,9 @@ def attn_fwd(qkv: torch.Tensor, B: int, L: int, H: int, dh: int, causal: bool = 
 
 def attn_bwd(qkv, out, dout, lse, B: int, L: int, H: int, dh: int, causal: bool = False,
              dqkv: Optional[torch.Tensor] = None, delta: Optional[torch.Tensor] = None, q_rows: int = 0):
+    """d(qkv) (bf16, the layout of ``qkv``) from ``out``, ``dout`` and the forward's ``lse``; the shapes of ``attn_fwd``
+    (head dims 32 / 64 / 80 up to 320 tokens; 64 non-causal at any length).  No float atomics: two calls give identical
+    bits.  At head dim 80, on the long-sequence path and with ``q_rows == 1`` every element of ``dqkv`` is written."""
     for t_, n in ((qkv, "qkv"), (out, "out"), (dout, "dout")):
         _req(t_, torch.bfloat16, n)
     if dqkv is None:
