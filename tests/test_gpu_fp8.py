@@ -215,7 +215,7 @@ def test_fp8_model_step_against_fp32_oracle_stated_tolerance():
 
 
 # ---------------------------------------------------------------------------------------------- round 3: fused quantisers
-@pytest.mark.parametrize("rows,d", [(197 * 3, 768), (257 * 2, 1024), (80, 512), (33, 128)])
+@pytest.mark.parametrize("rows,d", [(197 * 3, 768), (257 * 2, 1024), (80, 512), (33, 128), (257 * 2, 1280), (300, 2048)])
 def test_layernorm_forward_and_backward_emit_the_e4m3_copy(rows, d):
     """sc_layernorm_fwd_q8 / sc_layernorm_bwd_q8: the bf16 / fp32 outputs are bit-identical to the plain kernels', the
     e4m3 copy is the per-row power-of-two quantisation of the fp32 value the kernel holds (row scale in the top binade of
@@ -261,13 +261,16 @@ def test_layernorm_forward_and_backward_emit_the_e4m3_copy(rows, d):
     assert torch.equal(q8b, want)                       # same bits as torch's e4m3fn rounding of the fp32 result
 
 
-@pytest.mark.parametrize("rows,d,with_t8", [(4500, 1024, True), (300, 1024, False), (600, 768, True)])
+@pytest.mark.parametrize("rows,d,with_t8", [(4500, 1024, True), (300, 1024, False), (600, 768, True), (5140, 1280, True),
+                                             (300, 2048, False)])
 def test_lean_layernorm_backward_emits_the_same_e4m3_copies(rows, d, with_t8, monkeypatch):
     """The register-lean row body of the LayerNorm backward (round 5: bf16 rows + bf16 gradient stream; default at d = 1024,
     SC_LN_BWD_LEAN=3 also at d = 768) with the e4m3 copies: the new gradient is formed a third time once the row's scale is
     known.  Its per-row e4m3 copy is the quantisation of the very fp32 values it wrote (write_f32), its per-tensor copy uses
     the given scale, the recorded maximum is the tensor's; against the other body: bf16 outputs within one ulp on a few
-    elements, column sums to fp32 rounding.  4500 rows: more blocks than are resident."""
+    elements, column sums to fp32 rounding.  4500 rows: more blocks than are resident.  d = 1280 / 2048 (the NV = 8 body,
+    no lean variant: both settings run the same kernel) hold the e4m3 rules at the widest rows; 5140 rows at d = 1280 exceed
+    the 1024 nominal slots."""
     ops = _ops()
     g = torch.Generator().manual_seed(rows + d)
     x = (torch.randn(rows, d, generator=g) * 2 + 0.5).bfloat16().cuda()
