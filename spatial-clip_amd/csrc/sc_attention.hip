@@ -1,5 +1,5 @@
 // Multi-head self-attention for short sequences (L <= 320: ViT 197/257 tokens, CLIP text 77) on gfx950; longer ones go to
-// sc_attention_long.hip (see sc_attn_fwd / sc_attn_bwd at the end).
+// sc_attention_stream.hip, head dim 80 too (see sc_attn_fwd / sc_attn_bwd at the end).
 // One workgroup (4 waves) owns one (batch, head).  The whole K and V of that head sit in LDS (<= 80 KiB at
 // L=320, dh=64) in ONE swizzled image each that serves both row reads (ds_read_b128) and transposed reads
 // (ds_read_b64_tr_b16), so there is no multi-block online softmax and no [L,L] matrix in HBM.
@@ -491,10 +491,13 @@ static int attn_threads(int L, int max_waves) {
     return ((tiles + rounds - 1) / rounds) * 64;
 }
 
-// the streamed kernels of sc_attention_long.hip: above MAXL tokens (the only path there), or at any L with SC_ATTN_LONG=1
-// (A/B runs and tests; read per call, off by default)
-static bool attn_long(int B, int L, int H, int dh, int causal) {
-    if (B <= 0 || H <= 0 || L <= 0 || dh != 64 || causal) return false;
+// the streamed kernels of sc_attention_stream.hip take the call at head dim 80 (their only path, up to MAXL tokens) and
+// at head dim 64, non-causal, above MAXL tokens (the only path there) or at any L with SC_ATTN_LONG=1 (A/B runs and
+// tests; read per call, off by default)
+static bool attn_stream(int B, int L, int H, int dh, int causal) {
+    if (B <= 0 || H <= 0 || L <= 0) return false;
+    if (dh == 80) return L <= MAXL;
+    if (dh != 64 || causal) return false;
     if (L > MAXL) return true;
     const char* e = getenv("SC_ATTN_LONG");
     return e && e[0] == '1';
@@ -522,25 +525,17 @@ static int attn_check(const char* who, int B, int L, int H, int dh) {
 
 extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dh, int causal,
                            int q_rows, void* stream) {
-    if (attn_long(B, L, H, dh, causal)) {
+    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
+    hipStream_t st = (hipStream_t)stream;
+    if (attn_stream(B, L, H, dh, causal)) {
         if (attn_check_ptrs("sc_attn_fwd", qkv && out && lse, L)) return -1;
-        const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-        SC_CHECK(sc_attn_fwd_long(qkv, out, lse, B, L, Lq, H, dh, causal, (hipStream_t)stream),
+        SC_CHECK(sc_attn_fwd_stream(qkv, out, lse, B, L, Lq, H, dh, causal, st),
                  "sc_attn_fwd: grid too large (B=%d L=%d H=%d)", B, L, H);
         SC_LAUNCH_CHECK();
         return 0;
     }
     if (attn_check_long("sc_attn_fwd", L, dh, causal)) return -1;
     if (attn_check("sc_attn_fwd", B, L, H, dh)) return -1;
-    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-    hipStream_t st = (hipStream_t)stream;
-    if (dh == 80) {                                              // sc_attention_d80.hip: its own kernels, no switches
-        if (attn_check_ptrs("sc_attn_fwd", qkv && out && lse, L)) return -1;
-        SC_CHECK(sc_attn_fwd_d80(qkv, out, lse, B, L, Lq, H, dh, causal, st), "sc_attn_fwd: grid too large (B=%d L=%d H=%d)",
-                 B, L, H);
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
     const char* pe = getenv("SC_ATTN_PERSIST");                  // read per call, like SC_ATTN_BWD1 / SC_ATTN_BWD2
     const bool persist_on = !(pe && pe[0] == '0');
     if (persist_on && sc_attn_fwd_persistent(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
@@ -563,29 +558,19 @@ extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L,
 
 extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int L, int H, int dh, int causal, int q_rows, void* stream) {
-    if (attn_long(B, L, H, dh, causal)) {
+    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
+    hipStream_t st = (hipStream_t)stream;
+    if (attn_stream(B, L, H, dh, causal)) {
         if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
-        const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-        hipStream_t st = (hipStream_t)stream;
         // q_rows == 1 (class-token-only last block): the rank-one kernel streams the keys at any L
         if (!sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st))
-            SC_CHECK(sc_attn_bwd_long(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
+            SC_CHECK(sc_attn_bwd_stream(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
                      "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
         SC_LAUNCH_CHECK();
         return 0;
     }
     if (attn_check_long("sc_attn_bwd", L, dh, causal)) return -1;
     if (attn_check("sc_attn_bwd", B, L, H, dh)) return -1;
-    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-    hipStream_t st = (hipStream_t)stream;
-    if (dh == 80) {                                              // sc_attention_d80.hip; q_rows == 1 on the class-token kernel
-        if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
-        if (!sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st))
-            SC_CHECK(sc_attn_bwd_d80(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
-                     "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
-        SC_LAUNCH_CHECK();
-        return 0;
-    }
     const int Lp = (L + 31) & ~31;
     const float scale = 1.0f / sqrtf((float)dh);
     if (sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {      // q_rows == 1

@@ -35,19 +35,13 @@ int sc_attn_bwd_persistent(const void* qkv, const void* out, const void* dout, c
 int sc_attn_bwd_cls(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
                     int L, int Lq, int H, int dh, int causal, hipStream_t st);
 
-// sc_attention_long.hip: any L, dh = 64, non-causal; K / V (Q / dO) streamed through LDS in 64-row tiles.  Dispatched
-// above MAXL tokens, or at any L with SC_ATTN_LONG=1; 1 = launched, 0 = shape out of range
-int sc_attn_fwd_long(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                     hipStream_t st);
-int sc_attn_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                     int B, int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_d80.hip: head dim 80 (ViT-H), 0 < L <= 320, causal or not; K / V (Q / dO) streamed through LDS in 64-row
-// tiles of dense 160-byte rows; 1 = launched, 0 = shape out of range
-int sc_attn_fwd_d80(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                    hipStream_t st);
-int sc_attn_bwd_d80(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                    int L, int Lq, int H, int dh, int causal, hipStream_t st);
+// sc_attention_stream.hip: K / V (Q / dO) streamed through LDS in 64-row tiles.  dh = 64, non-causal, any L (dispatched
+// above MAXL tokens, or at any L with SC_ATTN_LONG=1) and dh = 80 (ViT-H), 0 < L <= MAXL, causal or not; 1 = launched,
+// 0 = shape out of range
+int sc_attn_fwd_stream(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
+                       hipStream_t st);
+int sc_attn_bwd_stream(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                       int B, int L, int Lq, int H, int dh, int causal, hipStream_t st);
 
 namespace {
 

@@ -99,7 +99,7 @@ _REGISTRY: Dict[str, ModelCfg] = {
     "ViT-S-16": _clip(384, 12, 384, 16, 384, 6),
     "ViT-S-32": _clip(384, 12, 384, 32, 384, 6),
     "ViT-Ti-16": _clip(512, 12, 192, 16, 256, 4),
-    # src/open_clip/model_configs/ViT-H-14.json, ViT-H-16.json: width 1280 = 16 heads of 80 (sc_attention_d80.hip), 32
+    # src/open_clip/model_configs/ViT-H-14.json, ViT-H-16.json: width 1280 = 16 heads of 80 (sc_attention_stream.hip), 32
     # layers, 257 / 197 tokens; text tower 1024 wide, 16 heads of 64, 24 layers
     "ViT-H-14": _clip(1024, 32, 1280, 14, 1024, 16, t_layers=24, head_width=80),
     "ViT-H-16": _clip(1024, 32, 1280, 16, 1024, 16, t_layers=24, head_width=80),

@@ -173,7 +173,7 @@ def workspace(nfloat: int, device, tag: str = "ws", dtype=torch.float32) -> torc
 def attn_fwd(qkv: torch.Tensor, B: int, L: int, H: int, dh: int, causal: bool = False,
              out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, q_rows: int = 0):
     """softmax(q k^T / sqrt(dh)) v on the packed bf16 ``qkv`` [B*L, 3*H*dh]: (out bf16 [B*L, H*dh], lse fp32 [B, H, L]).
-    Head dims 32 / 64 / 80 up to 320 tokens, causal or not (80: ViT-H, sc_attention_d80.hip); head dim 64 non-causal at any
+    Head dims 32 / 64 / 80 up to 320 tokens, causal or not (80: ViT-H, sc_attention_stream.hip); head dim 64 non-causal at any
     length.  Anything else raises RuntimeError naming the limit, before a launch.  ``q_rows`` > 0: only the first ``q_rows``
     query rows of every sequence are computed."""
     _req(qkv, torch.bfloat16, "qkv")

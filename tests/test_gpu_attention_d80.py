@@ -1,4 +1,4 @@
-"""Attention at head dim 80 (sc_attention_d80.hip; ViT-H): parity with the fp32 formula (non-causal and causal) at
+"""Attention at head dim 80 (sc_attention_stream.hip; ViT-H): parity with the fp32 formula (non-causal and causal) at
 lengths on, under and over the tile edges, large scores, q_rows, determinism, the shapes the build refuses, and head dims
 32 / 64 unchanged.  Formula and tolerances are those of tests/test_gpu_attention_long.py (out 2e-2, lse 2e-3 / 1e-3,
 dqkv 4e-2)."""

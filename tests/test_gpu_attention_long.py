@@ -1,5 +1,5 @@
-"""Attention above 320 tokens (sc_attention_long.hip): parity with the fp32 formula, q_rows, many heads, determinism,
-the SC_ATTN_LONG=1 switch at short lengths and the shapes the build rejects above 320 tokens."""
+"""Attention above 320 tokens (sc_attention_stream.hip at head dim 64): parity with the fp32 formula, q_rows, many heads,
+determinism, the SC_ATTN_LONG=1 switch at short lengths and the shapes the build rejects above 320 tokens."""
 import math
 
 import pytest

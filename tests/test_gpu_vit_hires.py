@@ -1,4 +1,4 @@
-"""Vision towers above 320 tokens end to end: ViT-L/14 at 336 px (577 tokens: attention on sc_attention_long.hip) against
+"""Vision towers above 320 tokens end to end: ViT-L/14 at 336 px (577 tokens: attention on sc_attention_stream.hip) against
 the fp32 oracle at reduced and full depth, training steps, graph replay, checkpoint resize, force_image_size and the
 training entry point with experiment=vitl14_336_gene_b64."""
 import functools

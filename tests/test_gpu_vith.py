@@ -1,4 +1,4 @@
-"""ViT-H towers (width 1280 = 16 heads of 80: attention on sc_attention_d80.hip) end to end: the reference's own
+"""ViT-H towers (width 1280 = 16 heads of 80: attention on sc_attention_stream.hip) end to end: the reference's own
 ResidualAttentionBlock at head dim 80 through one HIP block, ViT-H-14-gene against the fp32 oracle at reduced and full
 depth, ViT-H-16 with the reference text tower (causal head dim 64 beside head dim 80), training steps, graph replay,
 state_dict round trips, the construction-time refusal of 378 px and the training entry point with

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Attention forward / backward alone at head dim 80 (sc_attention_d80.hip; ViT-H): B=64, H=16 at L in {77 causal, 197,
+"""Attention forward / backward alone at head dim 80 (sc_attention_stream.hip; ViT-H): B=64, H=16 at L in {77 causal, 197,
 257} on Gaussian inputs, with F.scaled_dot_product_attention on the same tensors beside it and the in-tree dh = 64
 kernels at H = 20 (the same B * L * width, hence the same FLOP count) beside that.  TFLOP/s counts 4*B*H*L^2*dh
 (forward) and 10*B*H*L^2*dh (backward), causal or not.  The SDPA backend that the default call takes is named by timing

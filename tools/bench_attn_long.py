@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Attention forward / backward alone above 320 tokens (sc_attention_long.hip): B=64, H=16, dh=64 at
+"""Attention forward / backward alone above 320 tokens (sc_attention_stream.hip): B=64, H=16, dh=64 at
 L in {321, 401, 577, 785, 1025} on Gaussian inputs, with F.scaled_dot_product_attention on the same tensors beside it.
 TFLOP/s counts 4*B*H*L^2*dh (forward) and 10*B*H*L^2*dh (backward).  Then, at L = 197 and 257, the long kernels forced by
 SC_ATTN_LONG=1 against the in-tree kernels of that length, interleaved.
