@@ -523,6 +523,15 @@ static int attn_check(const char* who, int B, int L, int H, int dh) {
     return 0;
 }
 
+// the kernel the last call of each direction dispatched to (enum sc_attn_path); written at each `return 0` below
+static int attn_last_fwd = SC_ATTN_PATH_NONE, attn_last_bwd = SC_ATTN_PATH_NONE;
+
+extern "C" int sc_debug_attn_last_path(int* fwd, int* bwd) {
+    if (fwd) *fwd = attn_last_fwd;
+    if (bwd) *bwd = attn_last_bwd;
+    return 0;
+}
+
 extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dh, int causal,
                            int q_rows, void* stream) {
     const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
@@ -532,6 +541,7 @@ extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L,
         SC_CHECK(sc_attn_fwd_stream(qkv, out, lse, B, L, Lq, H, dh, causal, st),
                  "sc_attn_fwd: grid too large (B=%d L=%d H=%d)", B, L, H);
         SC_LAUNCH_CHECK();
+        attn_last_fwd = SC_ATTN_FWD_STREAM;
         return 0;
     }
     if (attn_check_long("sc_attn_fwd", L, dh, causal)) return -1;
@@ -540,11 +550,13 @@ extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L,
     const bool persist_on = !(pe && pe[0] == '0');
     if (persist_on && sc_attn_fwd_persistent(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
         SC_LAUNCH_CHECK();
+        attn_last_fwd = SC_ATTN_FWD_PERSISTENT;
         return 0;
     }
     const char* p2 = getenv("SC_ATTN_PERSIST2");                 // A/B switch of the 225..288-token persistent kernel
     if (persist_on && !(p2 && p2[0] == '0') && sc_attn_fwd_persistent2(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
         SC_LAUNCH_CHECK();
+        attn_last_fwd = SC_ATTN_FWD_PERSISTENT2;
         return 0;
     }
     const int Lp = (L + 31) & ~31;
@@ -553,6 +565,7 @@ extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L,
     const int nthreads = attn_threads(L, 13);
     SC_ATTN_DISPATCH(attn_fwd_kernel, (const bf16*)qkv, (bf16*)out, lse, L, Lq, H, scale);
     SC_LAUNCH_CHECK();
+    attn_last_fwd = SC_ATTN_FWD_PER_HEAD;
     return 0;
 }
 
@@ -563,10 +576,12 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
     if (attn_stream(B, L, H, dh, causal)) {
         if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
         // q_rows == 1 (class-token-only last block): the rank-one kernel streams the keys at any L
-        if (!sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st))
+        const bool cls = sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st) != 0;
+        if (!cls)
             SC_CHECK(sc_attn_bwd_stream(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
                      "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
         SC_LAUNCH_CHECK();
+        attn_last_bwd = cls ? SC_ATTN_BWD_CLS : SC_ATTN_BWD_STREAM;
         return 0;
     }
     if (attn_check_long("sc_attn_bwd", L, dh, causal)) return -1;
@@ -575,6 +590,7 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
     const float scale = 1.0f / sqrtf((float)dh);
     if (sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {      // q_rows == 1
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_CLS;
         return 0;
     }
     // 1) single-pass (non-causal, L <= 224): 232-256 us per ViT-B/16 layer; 2) persistent two-pass with loader waves
@@ -582,25 +598,30 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
     const bool ring_on = !(getenv("SC_ATTN_BWD3") && getenv("SC_ATTN_BWD3")[0] == '0');
     if (ring_on && sc_attn_bwd_ring(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {   // round 4: dS ring + MFMA-chain dQ
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_RING;
         return 0;
     }
     // round 5: 225..257 tokens (ViT-L/14): the ring design with eight key waves and no helper wave
     const bool ring8_on = !(getenv("SC_ATTN_BWD4") && getenv("SC_ATTN_BWD4")[0] == '0');
     if (ring8_on && sc_attn_bwd_ring8(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_RING8;
         return 0;
     }
     const bool single_on = !(getenv("SC_ATTN_BWD1") && getenv("SC_ATTN_BWD1")[0] == '0');
     if (single_on && sc_attn_bwd_single_pass(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_SINGLE_PASS;
         return 0;
     }
     const bool persist_on = !(getenv("SC_ATTN_BWD2") && getenv("SC_ATTN_BWD2")[0] == '0');
     if (persist_on && sc_attn_bwd_persistent(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_PERSISTENT;
         return 0;
     }
-    // fused two-pass kernel when Q, K, V and dO of a head fit LDS together (L <= 304 at dh = 64)
+    // fused two-pass kernel when Q, K, V and dO of a head fit LDS together (Lp = L rounded up to 32 rows: L <= 288 at
+    // dh = 64, every L <= MAXL at dh = 32); beyond that the dq + dkv pair
     const bool fused_on = !(getenv("SC_ATTN_FUSED") && getenv("SC_ATTN_FUSED")[0] == '0');
     const size_t lds_fused = (size_t)4 * Lp * dh * 2 + (size_t)2 * Lp * 4;
     if (fused_on && lds_fused <= 160 * 1024) {
@@ -609,6 +630,7 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
         SC_ATTN_DISPATCH(attn_bwd_fused_kernel, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
                          (bf16*)dqkv, L, Lq, H, scale);
         SC_LAUNCH_CHECK();
+        attn_last_bwd = SC_ATTN_BWD_FUSED;
         return 0;
     }
     const int nthreads = attn_threads(L, 7);
@@ -624,5 +646,6 @@ extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, c
                          scale);
         SC_LAUNCH_CHECK();
     }
+    attn_last_bwd = SC_ATTN_BWD_DQ_DKV;
     return 0;
 }

@@ -1,3 +1,14 @@
 // Internal alias of the public C ABI header (include/spatial_clip_hip.h).
 #pragma once
 #include "../../include/spatial_clip_hip.h"
+
+// Which kernel the last sc_attn_fwd / sc_attn_bwd of this process dispatched to (sc_debug_attn_last_path; tests assert that
+// a forced path really ran).  Host-side bookkeeping only: one int store per call.
+enum sc_attn_path {
+    SC_ATTN_PATH_NONE = -1,
+    // forward
+    SC_ATTN_FWD_PERSISTENT = 0, SC_ATTN_FWD_PERSISTENT2, SC_ATTN_FWD_PER_HEAD, SC_ATTN_FWD_STREAM,
+    // backward
+    SC_ATTN_BWD_CLS = 0, SC_ATTN_BWD_RING, SC_ATTN_BWD_RING8, SC_ATTN_BWD_SINGLE_PASS, SC_ATTN_BWD_PERSISTENT,
+    SC_ATTN_BWD_FUSED, SC_ATTN_BWD_DQ_DKV, SC_ATTN_BWD_STREAM
+};

@@ -202,6 +202,22 @@ def attn_bwd(qkv, out, dout, lse, B: int, L: int, H: int, dh: int, causal: bool 
     return dqkv
 
 
+# enum sc_attn_path (csrc/sc_kernels.h), in order
+ATTN_FWD_PATHS = ("persistent", "persistent2", "per_head", "stream")
+ATTN_BWD_PATHS = ("cls", "ring", "ring8", "single_pass", "persistent", "fused", "dq_dkv", "stream")
+
+
+def attn_last_path():
+    """(forward, backward): the names of the kernels that the last ``attn_fwd`` and the last ``attn_bwd`` of this process
+    dispatched to (``ATTN_FWD_PATHS`` / ``ATTN_BWD_PATHS``; ``"none"`` before the first call).  A debug hook
+    (``sc_debug_attn_last_path``): host-side bookkeeping, no device work."""
+    fn = getattr(_lib.lib(), "sc_debug_attn_last_path")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2
+    f, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    check(fn(ctypes.byref(f), ctypes.byref(b)), "sc_debug_attn_last_path")
+    return (ATTN_FWD_PATHS[f.value] if f.value >= 0 else "none", ATTN_BWD_PATHS[b.value] if b.value >= 0 else "none")
+
+
 # ------------------------------------------------------------------------------------------ norms
 def _t8_args(t8, rows: int, d: int, what: str):
     """(buffer uint8 [rows, >= d], scale fp32 [1], amax fp32 [64]) -> ctypes arguments of a per-tensor e4m3 second output."""

@@ -140,9 +140,16 @@ def test_forced_long_kernels_at_short_lengths(L, monkeypatch):
     res = {}
     for sw in ("0", "1"):
         monkeypatch.setenv("SC_ATTN_LONG", sw)
+        # what runs at these lengths without the switch: the persistent kernels up to 224 / 288 tokens forward, the ring
+        # kernels up to 224 / 257 backward, then the per-head kernels (300 tokens are past the fused backward's 288)
+        fwd, bwd = ("stream", "stream") if sw == "1" else {197: ("persistent", "ring"), 257: ("persistent2", "ring8"),
+                                                           300: ("per_head", "dq_dkv")}[L]
         out, lse = ops.attn_fwd(qkv, B, L, H, DH)
+        assert ops.attn_last_path()[0] == fwd
         out30, lse30 = ops.attn_fwd(qkv, B, L, H, DH, q_rows=30)
+        assert ops.attn_last_path()[0] == fwd
         dqkv = ops.attn_bwd(qkv, out, dout, lse, B, L, H, DH)
+        assert ops.attn_last_path()[1] == bwd
         torch.cuda.synchronize()
         _check(out, lse, dqkv, o_ref, lse_ref, g_ref)
         rows = (torch.arange(L, device="cuda") < 30).repeat(B)

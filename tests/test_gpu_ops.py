@@ -38,8 +38,9 @@ def ref_attn(qkv, B, L, H, dh, causal):
                                              (2, 77, 8, 64, True), (1, 257, 2, 64, False), (4, 16, 2, 32, True),
                                              (2, 64, 1, 64, False), (1, 320, 2, 64, False), (1, 310, 1, 64, True)])
 def test_attention_fwd_bwd(B, L, H, dh, causal):
-    # L <= 304 (dh = 64) takes the fused backward kernel (Q, K, V, dO of a head in LDS together), longer sequences the
-    # dq + dkv pair
+    # the default dispatch: up to 288 tokens at dh = 64 (any length at dh = 32) the kernels that decline a shape leave it to
+    # the fused backward kernel (Q, K, V, dO of a head in LDS together), longer sequences to the dq + dkv pair
+    # (tests/test_gpu_attention_sweep.py forces and names every path)
     ops = _ops()
     g = torch.Generator().manual_seed(L + dh)
     d = H * dh
@@ -105,6 +106,11 @@ def test_attention_fwd_persistent_vs_per_head_kernel(B, L, H, causal, q_rows, mo
         out = torch.full((B * L, d), 7.0, dtype=torch.bfloat16, device="cuda")
         lse = torch.full((B, H, L), 7.0, device="cuda")
         ops.attn_fwd(qd, B, L, H, dh, causal, out=out, lse=lse, q_rows=q_rows)
+        # the persistent kernel has one compute wave per 16-query tile beside 3 loader waves, 16 waves at most: above 208
+        # query rows it declines and the per-head kernel runs under either setting (225..288 tokens: sc_attention_p2.hip)
+        tiles = ((q_rows or L) + 15) // 16
+        want = "per_head" if persist == "0" or (L <= 224 and tiles + 3 > 16) else "persistent" if L <= 224 else "persistent2"
+        assert ops.attn_last_path()[0] == want
         outs.append((out.float().cpu().view(B, L, d), lse.cpu()))
     nq = q_rows if q_rows else L
     torch.testing.assert_close(outs[0][0][:, :nq], outs[1][0][:, :nq], atol=1.6e-2, rtol=1.6e-2)
@@ -137,9 +143,14 @@ def test_attention_bwd_paths_walk_many_heads(B, L, H, causal, path, monkeypatch)
     out, lse = ops.attn_fwd(qd, B, L, H, dh, causal)
     dq1 = torch.full((B * L, 3 * d), 7.0, dtype=torch.bfloat16, device="cuda")
     delta1 = torch.empty(B, H, L, device="cuda")
+    # ring and single-pass decline causal shapes: with the other switches off those cases fall to the fused per-head
+    # kernel, which is also what "per_head" selects at these lengths (by name, not silently)
+    want = "fused" if path == "per_head" or (causal and path in ("ring", "single_pass")) else path
     ops.attn_bwd(qd, out, gd, lse, B, L, H, dh, causal, dqkv=dq1, delta=delta1)
+    assert ops.attn_last_path()[1] == want
     dq2 = torch.full_like(dq1, 3.0)
     ops.attn_bwd(qd, out, gd, lse, B, L, H, dh, causal, dqkv=dq2)
+    assert ops.attn_last_path()[1] == want
     assert torch.equal(dq1, dq2)
     torch.testing.assert_close(dq1.float().cpu(), x.grad, atol=4e-2, rtol=4e-2)
     want_delta = (dout.float() * out.float().cpu()).view(B, L, H, dh).sum(-1).permute(0, 2, 1)
@@ -168,8 +179,10 @@ def test_attention_bwd_ring8_for_225_to_257_tokens(B, L, H, monkeypatch):
     dq1 = torch.full((B * L, 3 * d), 7.0, dtype=torch.bfloat16, device="cuda")
     delta1 = torch.full((B, H, L), 7.0, device="cuda")
     ops.attn_bwd(qd, out, gd, lse, B, L, H, dh, False, dqkv=dq1, delta=delta1)
+    assert ops.attn_last_path()[1] == "ring8"
     dq2 = torch.full_like(dq1, 3.0)
     ops.attn_bwd(qd, out, gd, lse, B, L, H, dh, False, dqkv=dq2)
+    assert ops.attn_last_path()[1] == "ring8"
     torch.cuda.synchronize()
     assert torch.equal(dq1, dq2)
     torch.testing.assert_close(dq1.float().cpu(), x.grad, atol=4e-2, rtol=4e-2)
@@ -178,6 +191,7 @@ def test_attention_bwd_ring8_for_225_to_257_tokens(B, L, H, monkeypatch):
     monkeypatch.setenv("SC_ATTN_BWD4", "0")
     dq3 = torch.full_like(dq1, 5.0)
     ops.attn_bwd(qd, out, gd, lse, B, L, H, dh, False, dqkv=dq3)
+    assert ops.attn_last_path()[1] == "fused"          # ring, single-pass and persistent stop at 224 tokens
     torch.testing.assert_close(dq1.float().cpu(), dq3.float().cpu(), atol=3e-2, rtol=3e-2)
     # the last token (row 256 at L = 257) is the stray key: its dK / dV rows on their own
     last = slice(L - 1, None, L)
