@@ -466,186 +466,213 @@ __global__ __launch_bounds__(1024) void attn_bwd_fused_kernel(const bf16* __rest
     }
 }
 
-template <typename K>
-void set_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)bytes);
-}
-
-}  // namespace
-
-#define SC_ATTN_DISPATCH(KERNEL, ...)                                                         \
-    do {                                                                                      \
-        if (dh == 64 && !causal) { set_lds(KERNEL<64, false>, lds); KERNEL<64, false><<<B * H, nthreads, lds, st>>>(__VA_ARGS__); } \
-        else if (dh == 64 && causal) { set_lds(KERNEL<64, true>, lds); KERNEL<64, true><<<B * H, nthreads, lds, st>>>(__VA_ARGS__); } \
-        else if (dh == 32 && !causal) { set_lds(KERNEL<32, false>, lds); KERNEL<32, false><<<B * H, nthreads, lds, st>>>(__VA_ARGS__); } \
-        else { set_lds(KERNEL<32, true>, lds); KERNEL<32, true><<<B * H, nthreads, lds, st>>>(__VA_ARGS__); } \
-    } while (0)
-
 // one wave per 16-row tile, all tiles of a head in flight at once when they fit (13 waves at L=197): balanced work
 // max_waves: 13 for forward (68 VGPRs -> 7 waves/SIMD, two 13-wave workgroups per CU so that one workgroup's K/V load
 // overlaps the other's compute); 7 for backward (114-120 VGPRs -> 4 waves/SIMD: two 7-wave workgroups per CU)
-static int attn_threads(int L, int max_waves) {
+int attn_threads(int L, int max_waves) {
     const int tiles = (L + 15) / 16;
     const int rounds = (tiles + max_waves - 1) / max_waves;
     return ((tiles + rounds - 1) / rounds) * 64;
 }
 
-// the streamed kernels of sc_attention_stream.hip take the call at head dim 80 (their only path, up to MAXL tokens) and
-// at head dim 64, non-causal, above MAXL tokens (the only path there) or at any L with SC_ATTN_LONG=1 (A/B runs and
-// tests; read per call, off by default)
-static bool attn_stream(int B, int L, int H, int dh, int causal) {
-    if (B <= 0 || H <= 0 || L <= 0) return false;
-    if (dh == 80) return L <= MAXL;
-    if (dh != 64 || causal) return false;
-    if (L > MAXL) return true;
-    const char* e = getenv("SC_ATTN_LONG");
-    return e && e[0] == '1';
+// ---------------------------------------------------------------------------------------------- the paths of this file
+// One workgroup per head: `images` LDS images of Lp = L rounded up to 32 rows and `vectors` fp32 row vectors.  The fused
+// backward holds Q, K, V and dO of a head (L <= 288 at dh = 64, every L <= MAXL at dh = 32); beyond that the dq + dkv pair.
+size_t per_head_lds(const AttnShape& s, int images, int vectors) {
+    const int Lp = (s.L + 31) & ~31;
+    return (size_t)images * Lp * s.dh * 2 + (size_t)vectors * Lp * 4;
+}
+bool per_head_accepts(const AttnShape& s) { return (s.dh == 64 || s.dh == 32) && s.L <= MAXL; }
+bool bwd_fused_accepts(const AttnShape& s) { return per_head_accepts(s) && per_head_lds(s, 4, 2) <= ATTN_LDS_MAX; }
+
+template <class F>
+void per_head_instance(const AttnShape& s, F&& f) {
+    attn_dispatch(attn_vals<32, 64>{}, s.dh, attn_vals<1, 0>{}, s.causal != 0, f);
 }
 
-static int attn_check_long(const char* who, int L, int dh, int causal) {
+int fwd_per_head_launch(const AttnShape& s, const AttnFwdOps& o, hipStream_t st) {
+    per_head_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_fwd_kernel<DH.value, C.value != 0>, s.nheads(), attn_threads(s.L, 13), per_head_lds(s, 2, 0), st, o.qkv,
+                    o.out, o.lse, s.L, s.Lq, s.H, s.scale());
+    });
+    return 0;
+}
+
+int bwd_fused_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    per_head_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_bwd_fused_kernel<DH.value, C.value != 0>, s.nheads(), attn_threads(s.L, 13), per_head_lds(s, 4, 2), st,
+                    o.qkv, o.out, o.dout, o.lse, o.delta, o.dqkv, s.L, s.Lq, s.H, s.scale());
+    });
+    return 0;
+}
+
+int bwd_dq_dkv_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    const int threads = attn_threads(s.L, 7);
+    per_head_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_bwd_dq_kernel<DH.value, C.value != 0>, s.nheads(), threads, per_head_lds(s, 2, 0), st, o.qkv, o.out,
+                    o.dout, o.lse, o.delta, o.dqkv, s.L, s.Lq, s.H, s.scale());
+    });
+    SC_LAUNCH_CHECK();
+    per_head_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_bwd_dkv_kernel<DH.value, C.value != 0>, s.nheads(), threads, per_head_lds(s, 2, 2), st, o.qkv, o.dout,
+                    o.lse, o.delta, o.dqkv, s.L, s.Lq, s.H, s.scale());
+    });
+    return 0;
+}
+
+// The streamed kernels of sc_attention_stream.hip are the only path at head dim 80 and above MAXL tokens; SC_ATTN_LONG=1
+// sends them the rest of their range too (head dim 64, non-causal, any L: A/B runs and tests).
+bool stream_only(const AttnShape& s) { return s.dh == 80 || s.L > MAXL; }
+bool fwd_stream_only(const AttnShape& s) { return stream_only(s) && sc_attn_fwd_stream_accepts(s); }
+bool bwd_stream_only(const AttnShape& s) { return stream_only(s) && sc_attn_bwd_stream_accepts(s); }
+
+// ---------------------------------------------------------------------------------------------- the path tables
+// Which kernel runs for a shape: the first entry, in table order, whose switches are on and whose predicate accepts it.
+// A switch is an environment variable read per call (tests select a path): opt-out ones are on unless set to 0, the opt-in
+// one is on when set to 1.
+struct AttnSwitch {
+    const char* name;
+    bool opt_in;
+};
+template <class Ops>
+struct AttnPath {
+    int id;                                   // enum sc_attn_path
+    AttnSwitch sw[2];
+    bool (*accepts)(const AttnShape&);
+    int (*launch)(const AttnShape&, const Ops&, hipStream_t);
+};
+
+const AttnPath<AttnFwdOps> attn_fwd_paths[] = {
+    {SC_ATTN_FWD_STREAM, {}, fwd_stream_only, sc_attn_fwd_stream_launch},
+    {SC_ATTN_FWD_STREAM, {{"SC_ATTN_LONG", true}}, sc_attn_fwd_stream_accepts, sc_attn_fwd_stream_launch},
+    {SC_ATTN_FWD_PERSISTENT, {{"SC_ATTN_PERSIST"}}, sc_attn_fwd_persistent_accepts, sc_attn_fwd_persistent_launch},
+    {SC_ATTN_FWD_PERSISTENT2, {{"SC_ATTN_PERSIST"}, {"SC_ATTN_PERSIST2"}}, sc_attn_fwd_persistent2_accepts,
+     sc_attn_fwd_persistent2_launch},
+    {SC_ATTN_FWD_PER_HEAD, {}, per_head_accepts, fwd_per_head_launch},
+};
+
+// the per-layer times behind this order (ViT-B/16, 197 tokens): ring 180-183 us, single pass 232-256 us, persistent two-pass
+// (also causal) 254 us, one workgroup per head 268-296 us
+const AttnPath<AttnBwdOps> attn_bwd_paths[] = {
+    {SC_ATTN_BWD_CLS, {}, sc_attn_bwd_cls_accepts, sc_attn_bwd_cls_launch},
+    {SC_ATTN_BWD_STREAM, {}, bwd_stream_only, sc_attn_bwd_stream_launch},
+    {SC_ATTN_BWD_STREAM, {{"SC_ATTN_LONG", true}}, sc_attn_bwd_stream_accepts, sc_attn_bwd_stream_launch},
+    {SC_ATTN_BWD_RING, {{"SC_ATTN_BWD3"}}, sc_attn_bwd_ring_accepts, sc_attn_bwd_ring_launch},
+    {SC_ATTN_BWD_RING8, {{"SC_ATTN_BWD4"}}, sc_attn_bwd_ring8_accepts, sc_attn_bwd_ring8_launch},
+    {SC_ATTN_BWD_SINGLE_PASS, {{"SC_ATTN_BWD1"}}, sc_attn_bwd_single_pass_accepts, sc_attn_bwd_single_pass_launch},
+    {SC_ATTN_BWD_PERSISTENT, {{"SC_ATTN_BWD2"}}, sc_attn_bwd_persistent_accepts, sc_attn_bwd_persistent_launch},
+    {SC_ATTN_BWD_FUSED, {{"SC_ATTN_FUSED"}}, bwd_fused_accepts, bwd_fused_launch},
+    {SC_ATTN_BWD_DQ_DKV, {}, per_head_accepts, bwd_dq_dkv_launch},
+};
+
+bool attn_switch_on(const AttnSwitch& w) {
+    const char* e = w.name ? getenv(w.name) : nullptr;
+    return w.opt_in ? (e && e[0] == '1') : !(e && e[0] == '0');
+}
+
+// the chosen entry, or nullptr: a streamed shape whose grid does not fit (every other valid shape has a per-head kernel)
+template <class Ops, size_t N>
+const AttnPath<Ops>* attn_plan(const AttnPath<Ops> (&table)[N], const AttnShape& s) {
+    for (const AttnPath<Ops>& e : table)
+        if (e.accepts(s) && attn_switch_on(e.sw[0]) && attn_switch_on(e.sw[1])) return &e;
+    return nullptr;
+}
+const AttnPath<AttnFwdOps>* attn_plan_fwd(const AttnShape& s) { return attn_plan(attn_fwd_paths, s); }
+const AttnPath<AttnBwdOps>* attn_plan_bwd(const AttnShape& s) { return attn_plan(attn_bwd_paths, s); }
+
+// ---------------------------------------------------------------------------------------------- validation
+int attn_validate(const char* who, int B, int L, int H, int dh, int causal) {
     SC_CHECK(L <= MAXL || (dh == 64 && !causal),
              "%s: above %d tokens only non-causal attention with head dim 64 is supported; head dims 32 / 64 / 80, causal or "
              "not, up to %d tokens (L=%d, dh=%d, causal=%d)", who, MAXL, MAXL, L, dh, causal);
+    SC_CHECK(B > 0 && H > 0 && L > 0, "%s: need 0 < L <= %d (L=%d), B=%d H=%d", who, MAXL, L, B, H);
+    SC_CHECK(dh == 64 || dh == 32 || dh == 80, "%s: head dim must be 32, 64 or 80 (got %d)", who, dh);
     return 0;
 }
 
 // a launch on a null operand would fault the device: refused before anything is enqueued
-static int attn_check_ptrs(const char* who, bool ok, int L) {
+int attn_check_ptrs(const char* who, bool ok, int L) {
     SC_CHECK(ok, "%s: null operand pointer (supported: 0 < L <= %d with dh 32 / 64 / 80, causal or not; any L with dh 64, "
                  "non-causal; got L=%d)", who, MAXL, L);
     return 0;
 }
 
-static int attn_check(const char* who, int B, int L, int H, int dh) {
-    SC_CHECK(B > 0 && H > 0 && L > 0 && L <= MAXL, "%s: need 0 < L <= %d (L=%d), B=%d H=%d", who, MAXL, L, B, H);
-    SC_CHECK(dh == 64 || dh == 32 || dh == 80, "%s: head dim must be 32, 64 or 80 (got %d)", who, dh);
-    return 0;
+AttnShape attn_shape(int B, int L, int H, int dh, int causal, int q_rows) {
+    return {B, L, (q_rows > 0 && q_rows < L) ? q_rows : L, H, dh, causal};
 }
 
-// the kernel the last call of each direction dispatched to (enum sc_attn_path); written at each `return 0` below
-static int attn_last_fwd = SC_ATTN_PATH_NONE, attn_last_bwd = SC_ATTN_PATH_NONE;
+// the kernel the last call of each direction dispatched to (enum sc_attn_path)
+int attn_last_fwd = SC_ATTN_PATH_NONE, attn_last_bwd = SC_ATTN_PATH_NONE;
 
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------- shared launch helpers
+static int attn_cu_count() {
+    static int ncu = 0;
+    if (!ncu) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
+        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    }
+    return ncu;
+}
+
+int attn_persistent_grid(int nheads) {
+    const int ncu = attn_cu_count();
+    if (!ncu) sc_set_error("attention: the device's compute-unit count cannot be read (the device query failed)");
+    return nheads < ncu ? nheads : ncu;
+}
+
+int attn_grid_cap(int grid) {
+    const char* e = getenv("SC_ATTN_GRID");
+    const int cap = e ? atoi(e) : 0;
+    return cap > 0 && cap < grid ? cap : grid;
+}
+
+// ---------------------------------------------------------------------------------------------- the C ABI
 extern "C" int sc_debug_attn_last_path(int* fwd, int* bwd) {
     if (fwd) *fwd = attn_last_fwd;
     if (bwd) *bwd = attn_last_bwd;
     return 0;
 }
 
+// the paths the next sc_attn_fwd / sc_attn_bwd of this shape would take under the current environment; no HIP call
+extern "C" int sc_debug_attn_plan(int B, int L, int H, int dh, int causal, int q_rows, int* fwd, int* bwd) {
+    if (attn_validate("sc_attn_fwd", B, L, H, dh, causal)) return -1;
+    const AttnShape s = attn_shape(B, L, H, dh, causal, q_rows);
+    const AttnPath<AttnFwdOps>* f = attn_plan_fwd(s);
+    SC_CHECK(f, "sc_attn_fwd: grid too large (B=%d L=%d H=%d)", B, L, H);
+    const AttnPath<AttnBwdOps>* b = attn_plan_bwd(s);
+    SC_CHECK(b, "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
+    if (fwd) *fwd = f->id;
+    if (bwd) *bwd = b->id;
+    return 0;
+}
+
 extern "C" int sc_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dh, int causal,
                            int q_rows, void* stream) {
-    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-    hipStream_t st = (hipStream_t)stream;
-    if (attn_stream(B, L, H, dh, causal)) {
-        if (attn_check_ptrs("sc_attn_fwd", qkv && out && lse, L)) return -1;
-        SC_CHECK(sc_attn_fwd_stream(qkv, out, lse, B, L, Lq, H, dh, causal, st),
-                 "sc_attn_fwd: grid too large (B=%d L=%d H=%d)", B, L, H);
-        SC_LAUNCH_CHECK();
-        attn_last_fwd = SC_ATTN_FWD_STREAM;
-        return 0;
-    }
-    if (attn_check_long("sc_attn_fwd", L, dh, causal)) return -1;
-    if (attn_check("sc_attn_fwd", B, L, H, dh)) return -1;
-    const char* pe = getenv("SC_ATTN_PERSIST");                  // read per call, like SC_ATTN_BWD1 / SC_ATTN_BWD2
-    const bool persist_on = !(pe && pe[0] == '0');
-    if (persist_on && sc_attn_fwd_persistent(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
-        SC_LAUNCH_CHECK();
-        attn_last_fwd = SC_ATTN_FWD_PERSISTENT;
-        return 0;
-    }
-    const char* p2 = getenv("SC_ATTN_PERSIST2");                 // A/B switch of the 225..288-token persistent kernel
-    if (persist_on && !(p2 && p2[0] == '0') && sc_attn_fwd_persistent2(qkv, out, lse, B, L, Lq, H, dh, causal, st)) {
-        SC_LAUNCH_CHECK();
-        attn_last_fwd = SC_ATTN_FWD_PERSISTENT2;
-        return 0;
-    }
-    const int Lp = (L + 31) & ~31;
-    const size_t lds = (size_t)2 * Lp * dh * 2;
-    const float scale = 1.0f / sqrtf((float)dh);
-    const int nthreads = attn_threads(L, 13);
-    SC_ATTN_DISPATCH(attn_fwd_kernel, (const bf16*)qkv, (bf16*)out, lse, L, Lq, H, scale);
+    if (attn_validate("sc_attn_fwd", B, L, H, dh, causal)) return -1;
+    if (attn_check_ptrs("sc_attn_fwd", qkv && out && lse, L)) return -1;
+    const AttnShape s = attn_shape(B, L, H, dh, causal, q_rows);
+    const AttnPath<AttnFwdOps>* e = attn_plan_fwd(s);
+    SC_CHECK(e, "sc_attn_fwd: grid too large (B=%d L=%d H=%d)", B, L, H);
+    if (const int rc = e->launch(s, {(const bf16*)qkv, (bf16*)out, lse}, (hipStream_t)stream)) return rc;
     SC_LAUNCH_CHECK();
-    attn_last_fwd = SC_ATTN_FWD_PER_HEAD;
+    attn_last_fwd = e->id;
     return 0;
 }
 
 extern "C" int sc_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int L, int H, int dh, int causal, int q_rows, void* stream) {
-    const int Lq = (q_rows > 0 && q_rows < L) ? q_rows : L;
-    hipStream_t st = (hipStream_t)stream;
-    if (attn_stream(B, L, H, dh, causal)) {
-        if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
-        // q_rows == 1 (class-token-only last block): the rank-one kernel streams the keys at any L
-        const bool cls = sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st) != 0;
-        if (!cls)
-            SC_CHECK(sc_attn_bwd_stream(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st),
-                     "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = cls ? SC_ATTN_BWD_CLS : SC_ATTN_BWD_STREAM;
-        return 0;
-    }
-    if (attn_check_long("sc_attn_bwd", L, dh, causal)) return -1;
-    if (attn_check("sc_attn_bwd", B, L, H, dh)) return -1;
-    const int Lp = (L + 31) & ~31;
-    const float scale = 1.0f / sqrtf((float)dh);
-    if (sc_attn_bwd_cls(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {      // q_rows == 1
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_CLS;
-        return 0;
-    }
-    // 1) single-pass (non-causal, L <= 224): 232-256 us per ViT-B/16 layer; 2) persistent two-pass with loader waves
-    // (also causal): 254 us; 3) one workgroup per head: 268-296 us.  The switches are read per call (tests select a path).
-    const bool ring_on = !(getenv("SC_ATTN_BWD3") && getenv("SC_ATTN_BWD3")[0] == '0');
-    if (ring_on && sc_attn_bwd_ring(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {   // round 4: dS ring + MFMA-chain dQ
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_RING;
-        return 0;
-    }
-    // round 5: 225..257 tokens (ViT-L/14): the ring design with eight key waves and no helper wave
-    const bool ring8_on = !(getenv("SC_ATTN_BWD4") && getenv("SC_ATTN_BWD4")[0] == '0');
-    if (ring8_on && sc_attn_bwd_ring8(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_RING8;
-        return 0;
-    }
-    const bool single_on = !(getenv("SC_ATTN_BWD1") && getenv("SC_ATTN_BWD1")[0] == '0');
-    if (single_on && sc_attn_bwd_single_pass(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_SINGLE_PASS;
-        return 0;
-    }
-    const bool persist_on = !(getenv("SC_ATTN_BWD2") && getenv("SC_ATTN_BWD2")[0] == '0');
-    if (persist_on && sc_attn_bwd_persistent(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, dh, causal, st)) {
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_PERSISTENT;
-        return 0;
-    }
-    // fused two-pass kernel when Q, K, V and dO of a head fit LDS together (Lp = L rounded up to 32 rows: L <= 288 at
-    // dh = 64, every L <= MAXL at dh = 32); beyond that the dq + dkv pair
-    const bool fused_on = !(getenv("SC_ATTN_FUSED") && getenv("SC_ATTN_FUSED")[0] == '0');
-    const size_t lds_fused = (size_t)4 * Lp * dh * 2 + (size_t)2 * Lp * 4;
-    if (fused_on && lds_fused <= 160 * 1024) {
-        const size_t lds = lds_fused;
-        const int nthreads = attn_threads(L, 13);
-        SC_ATTN_DISPATCH(attn_bwd_fused_kernel, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                         (bf16*)dqkv, L, Lq, H, scale);
-        SC_LAUNCH_CHECK();
-        attn_last_bwd = SC_ATTN_BWD_FUSED;
-        return 0;
-    }
-    const int nthreads = attn_threads(L, 7);
-    {
-        const size_t lds = (size_t)2 * Lp * dh * 2;
-        SC_ATTN_DISPATCH(attn_bwd_dq_kernel, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                         (bf16*)dqkv, L, Lq, H, scale);
-        SC_LAUNCH_CHECK();
-    }
-    {
-        const size_t lds = (size_t)2 * Lp * dh * 2 + (size_t)2 * Lp * 4;
-        SC_ATTN_DISPATCH(attn_bwd_dkv_kernel, (const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv, L, Lq, H,
-                         scale);
-        SC_LAUNCH_CHECK();
-    }
-    attn_last_bwd = SC_ATTN_BWD_DQ_DKV;
+    if (attn_validate("sc_attn_bwd", B, L, H, dh, causal)) return -1;
+    if (attn_check_ptrs("sc_attn_bwd", qkv && out && dout && lse && delta && dqkv, L)) return -1;
+    const AttnShape s = attn_shape(B, L, H, dh, causal, q_rows);
+    const AttnPath<AttnBwdOps>* e = attn_plan_bwd(s);
+    SC_CHECK(e, "sc_attn_bwd: grid too large (B=%d L=%d H=%d)", B, L, H);
+    const AttnBwdOps o{(const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv};
+    if (const int rc = e->launch(s, o, (hipStream_t)stream)) return rc;
+    SC_LAUNCH_CHECK();
+    attn_last_bwd = e->id;
     return 0;
 }

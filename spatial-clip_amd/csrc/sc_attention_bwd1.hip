@@ -24,7 +24,6 @@
 // of 246 VGPRs per CU the sweep is latency-bound (35 LDS / MFMA waits per step and wave), not pipe-bound.
 //   reference: autograd of nn.MultiheadAttention's SDPA, src/open_clip/transformer.py:253,272-287; mask :1080-1086.
 #include "sc_attn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -349,53 +348,31 @@ __global__ __launch_bounds__(512) void attn_bwd1_kernel(const bf16* __restrict__
     }
 }
 
-template <typename K>
-void set_lds_b(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-template <int NB>
-void launch_bwd1(bool causal, int grid, size_t lds, hipStream_t st, const bf16* qkv, const bf16* out, const bf16* dout,
-                 const float* lse, float* delta, bf16* dqkv, int L, int H, int nheads, float scale, unsigned dqb) {
-    (void)causal;       // causal instances exceed the 256-VGPR budget (mask arithmetic on every block): the text tower
-                        // keeps the two-pass kernel
-    set_lds_b(attn_bwd1_kernel<NB, false>, lds);
-    attn_bwd1_kernel<NB, false><<<grid, (NB + 1) * 64, lds, st>>>(qkv, out, dout, lse, delta, dqkv, L, H, nheads, scale, dqb);
+// NB key waves + the helper wave; K, V, dO images, the fp32 dQ accumulator, one dS tile per wave, four row vectors
+struct Bwd1Geom {
+    int NB;
+    size_t lds;
+    bool ok;
+};
+Bwd1Geom bwd1_geom(const AttnShape& s) {
+    const int NB = (s.L + 31) / 32, Lp = NB * 32;
+    const size_t lds = (size_t)3 * Lp * BDH * 2 + (size_t)Lp * BDH * 4 + (size_t)NB * 2048 + (size_t)4 * Lp * 4 + 64;
+    // causal instances exceed the 256-VGPR budget (mask arithmetic on every block): the text tower keeps the two-pass kernel
+    return {NB, lds,
+            s.dh == BDH && s.L <= 224 && s.Lq == s.L && !s.causal && lds <= ATTN_LDS_MAX && attn_fits_buffer(s.dqkv_bytes())};
 }
 
 }  // namespace
 
-// returns 1 if the single-pass kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_bwd_single_pass(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                            int B, int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (dh != BDH || L > 224 || Lq != L || causal) return 0;
-    const int NB = (L + 31) / 32;
-    const int Lp = NB * 32;
-    const size_t lds = (size_t)3 * Lp * dh * 2 + (size_t)Lp * dh * 4 + (size_t)NB * 2048 + (size_t)4 * Lp * 4 + 64;
-    const long long dqb = (long long)B * L * 3 * H * dh * 2;
-    if (dqb >= 0xFFFFFFF0ll) return 0;
-    if (lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int nheads = B * H;
-    const int grid = nheads < ncu ? nheads : ncu;
-    const float scale = 1.0f / sqrtf((float)dh);
-    const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *g = (const bf16*)dout;
-    bf16* dq = (bf16*)dqkv;
-    switch (NB) {
-        case 1: launch_bwd1<1>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 2: launch_bwd1<2>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 3: launch_bwd1<3>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 4: launch_bwd1<4>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 5: launch_bwd1<5>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 6: launch_bwd1<6>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 7: launch_bwd1<7>(causal, grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        default: return 0;
-    }
-    return 1;
+bool sc_attn_bwd_single_pass_accepts(const AttnShape& s) { return bwd1_geom(s).ok; }
+
+int sc_attn_bwd_single_pass_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    const Bwd1Geom g = bwd1_geom(s);
+    const int grid = attn_persistent_grid(s.nheads());
+    if (!grid) return -1;
+    attn_dispatch(attn_blocks7{}, g.NB, [&](auto NB) {
+        attn_launch(attn_bwd1_kernel<NB.value, false>, grid, (g.NB + 1) * 64, g.lds, st, o.qkv, o.out, o.dout, o.lse, o.delta,
+                    o.dqkv, s.L, s.H, s.nheads(), s.scale(), (unsigned)s.dqkv_bytes());
+    });
+    return 0;
 }

@@ -21,7 +21,6 @@
 // LDS at L = 197: 4 x 28 KiB images + 14 x 2 KiB staging + 1.75 KiB statistics = 141.8 KiB.
 //   reference: autograd of nn.MultiheadAttention's SDPA, src/open_clip/transformer.py:253,272-287; mask :1080-1086.
 #include "sc_attn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -324,30 +323,18 @@ __global__ __launch_bounds__(1024) void attn_bwd2_kernel(const bf16* __restrict_
     }
 }
 
-template <typename K>
-void set_lds_2(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-struct Bwd2Args {
-    const bf16 *qkv, *out, *dout;
-    const float* lse;
-    float* delta;
-    bf16* dqkv;
-    int L, H, nheads;
-    float scale;
-    unsigned dqb;
+// one compute wave per 16-row tile + the loader waves; Q, K, V, dO images, two dS tiles per key block, two row vectors
+struct Bwd2Geom {
+    int NB, threads;
+    size_t lds;
+    bool ok;
 };
-
-template <int NB>
-void launch_bwd2(bool causal, int grid, int threads, size_t lds, hipStream_t st, const Bwd2Args& a) {
-    if (causal) {
-        set_lds_2(attn_bwd2_kernel<NB, true>, lds);
-        attn_bwd2_kernel<NB, true><<<grid, threads, lds, st>>>(a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv, a.L, a.H, a.nheads, a.scale, a.dqb);
-    } else {
-        set_lds_2(attn_bwd2_kernel<NB, false>, lds);
-        attn_bwd2_kernel<NB, false><<<grid, threads, lds, st>>>(a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv, a.L, a.H, a.nheads, a.scale, a.dqb);
-    }
+Bwd2Geom bwd2_geom(const AttnShape& s) {
+    const int nt = (s.L + 15) / 16, NB = (s.L + 31) / 32, Lp = NB * 32;
+    const size_t lds = (size_t)4 * Lp * PDH * 2 + (size_t)2 * NB * 2048 + (size_t)2 * Lp * 4 + 64;
+    return {NB, (nt + NLOADER) * 64, lds,
+            s.dh == PDH && s.L <= 224 && s.Lq == s.L && nt + NLOADER <= 16 && lds <= ATTN_LDS_MAX &&
+                attn_fits_buffer(s.dqkv_bytes())};
 }
 
 }  // namespace
@@ -358,37 +345,15 @@ extern "C" int sc_debug_attn_trace(unsigned long long* host_out) {
 }
 #endif
 
-// returns 1 if this kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_bwd_persistent(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                           int B, int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (dh != PDH || L > 224 || Lq != L) return 0;
-    const int nt = (L + 15) / 16, NB = (L + 31) / 32;
-    if (nt + NLOADER > 16) return 0;
-    const int Lp = NB * 32;
-    const size_t lds = (size_t)4 * Lp * dh * 2 + (size_t)2 * NB * 2048 + (size_t)2 * Lp * 4 + 64;
-    const long long dqb = (long long)B * L * 3 * H * dh * 2;
-    if (dqb >= 0xFFFFFFF0ll || lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int nheads = B * H;
-    const int grid = nheads < ncu ? nheads : ncu;
-    const int threads = (nt + NLOADER) * 64;
-    const Bwd2Args a{(const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, L, H, nheads,
-                     1.0f / sqrtf((float)dh), (unsigned)dqb};
-    switch (NB) {
-        case 1: launch_bwd2<1>(causal, grid, threads, lds, st, a); break;
-        case 2: launch_bwd2<2>(causal, grid, threads, lds, st, a); break;
-        case 3: launch_bwd2<3>(causal, grid, threads, lds, st, a); break;
-        case 4: launch_bwd2<4>(causal, grid, threads, lds, st, a); break;
-        case 5: launch_bwd2<5>(causal, grid, threads, lds, st, a); break;
-        case 6: launch_bwd2<6>(causal, grid, threads, lds, st, a); break;
-        case 7: launch_bwd2<7>(causal, grid, threads, lds, st, a); break;
-        default: return 0;
-    }
-    return 1;
+bool sc_attn_bwd_persistent_accepts(const AttnShape& s) { return bwd2_geom(s).ok; }
+
+int sc_attn_bwd_persistent_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    const Bwd2Geom g = bwd2_geom(s);
+    const int grid = attn_persistent_grid(s.nheads());
+    if (!grid) return -1;
+    attn_dispatch(attn_blocks7{}, g.NB, attn_causal{}, s.causal != 0, [&](auto NB, auto C) {
+        attn_launch(attn_bwd2_kernel<NB.value, C.value != 0>, grid, g.threads, g.lds, st, o.qkv, o.out, o.dout, o.lse, o.delta,
+                    o.dqkv, s.L, s.H, s.nheads(), s.scale(), (unsigned)s.dqkv_bytes());
+    });
+    return 0;
 }

@@ -27,7 +27,6 @@
 //   tail     += 1 by the helper when the last block's rows of the next head have landed -> key waves before their last block
 //   reference: autograd of nn.MultiheadAttention's SDPA, src/open_clip/transformer.py:253,272-287.
 #include "sc_attn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -379,51 +378,32 @@ __global__ __launch_bounds__(512) void attn_bwd3_kernel(const bf16* __restrict__
 #endif
 }
 
-template <int NB>
-void launch_bwd3(int grid, size_t lds, hipStream_t st, const bf16* qkv, const bf16* out, const bf16* dout, const float* lse,
-                 float* delta, bf16* dqkv, int L, int H, int nheads, float scale, unsigned dqb) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd3_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    attn_bwd3_kernel<NB><<<grid, (NB + 1) * 64, lds, st>>>(qkv, out, dout, lse, delta, dqkv, L, H, nheads, scale, dqb);
+// NB key waves + the helper wave; Q, K, V, dO images, the ring of dS tiles, four row vectors, the ring's counters
+struct Bwd3Geom {
+    int NB;
+    size_t lds;
+    bool ok;
+};
+Bwd3Geom bwd3_geom(const AttnShape& s) {
+    const int NB = (s.L + 31) / 32, Lp = NB * 32;
+    const size_t lds = (size_t)4 * Lp * BDH * 2 + (size_t)RING * NB * 2048 + (size_t)4 * Lp * 4 + (size_t)(2 * NB + 1) * 4 + 60;
+    return {NB, lds,
+            s.dh == BDH && s.L <= 224 && s.Lq == s.L && !s.causal && lds <= ATTN_LDS_MAX && attn_fits_buffer(s.dqkv_bytes())};
 }
 
 }  // namespace
 
-// returns 1 if the kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_bwd_ring(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                     int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (dh != BDH || L > 224 || Lq != L || causal) return 0;
-    const int NB = (L + 31) / 32;
-    const int Lp = NB * 32;
-    const size_t lds = (size_t)4 * Lp * dh * 2 + (size_t)RING * NB * 2048 + (size_t)4 * Lp * 4 + (size_t)(2 * NB + 1) * 4 + 60;
-    const long long dqb = (long long)B * L * 3 * H * dh * 2;
-    if (dqb >= 0xFFFFFFF0ll) return 0;
-    if (lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int nheads = B * H;
-    int grid = nheads < ncu ? nheads : ncu;
-    if (const char* e = getenv("SC_ATTN_GRID")) { const int gcap = atoi(e); if (gcap > 0 && gcap < grid) grid = gcap; }   // measurement: fewer workgroups
+bool sc_attn_bwd_ring_accepts(const AttnShape& s) { return bwd3_geom(s).ok; }
 
-    const float scale = 1.0f / sqrtf((float)dh);
-    const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *g = (const bf16*)dout;
-    bf16* dq = (bf16*)dqkv;
-    switch (NB) {
-        case 1: launch_bwd3<1>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 2: launch_bwd3<2>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 3: launch_bwd3<3>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 4: launch_bwd3<4>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 5: launch_bwd3<5>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 6: launch_bwd3<6>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        case 7: launch_bwd3<7>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb); break;
-        default: return 0;
-    }
-    return 1;
+int sc_attn_bwd_ring_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    const Bwd3Geom g = bwd3_geom(s);
+    const int grid = attn_grid_cap(attn_persistent_grid(s.nheads()));
+    if (!grid) return -1;
+    attn_dispatch(attn_blocks7{}, g.NB, [&](auto NB) {
+        attn_launch(attn_bwd3_kernel<NB.value>, grid, (g.NB + 1) * 64, g.lds, st, o.qkv, o.out, o.dout, o.lse, o.delta, o.dqkv,
+                    s.L, s.H, s.nheads(), s.scale(), (unsigned)s.dqkv_bytes());
+    });
+    return 0;
 }
 
 #ifdef SC_BWD3_CLOCK

@@ -38,7 +38,6 @@
 // LDS (L = 257): Q, dO images 2 x 33 KiB (264 rows), K image 32 KiB, ring 48 KiB, statistics 4.1 KiB, partial sums 6 KiB,
 // scratch = 158.8 KiB.
 #include "sc_attn_common.h"
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -711,12 +710,20 @@ __global__ __launch_bounds__(512) void attn_bwd4_kernel(const bf16* __restrict__
     }
 }
 
-template <int NBQ>
-void launch_bwd4(int grid, size_t lds, hipStream_t st, const bf16* qkv, const bf16* out, const bf16* dout, const float* lse,
-                 float* delta, bf16* dqkv, int L, int H, int nheads, float scale, unsigned dqb) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd4_kernel<NBQ>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    attn_bwd4_kernel<NBQ><<<grid, B4NW * 64, lds, st>>>(qkv, out, dout, lse, delta, dqkv, L, H, nheads, scale, dqb);
+// query blocks: 8, or 9 at L = 257 (block 8 = the single row 256, with 264-row Q / dO images and a second reducer strip)
+struct Bwd4Geom {
+    int NBQ;
+    size_t lds;
+    bool ok;
+};
+Bwd4Geom bwd4_geom(const AttnShape& s) {
+    const int NBQ = s.L > 256 ? 9 : 8, rows = NBQ == 9 ? 264 : 256;
+    const size_t lds = (size_t)2 * rows * B4DH * 2 + (size_t)256 * B4DH * 2 + (size_t)B4RING * B4NW * 2048 + (size_t)4 * rows * 4 +
+                       (size_t)B4NW * 128 * 4 + 512 + (size_t)B4NW * 64 * 4 + (NBQ == 9 ? (size_t)B4NW * 64 * 4 : 0) +
+                       (size_t)(2 * NBQ + 2) * 4 + 56;
+    return {NBQ, lds,
+            s.dh == B4DH && s.L > 224 && s.L <= 257 && s.Lq == s.L && !s.causal && lds <= ATTN_LDS_MAX &&
+                attn_fits_buffer(s.dqkv_bytes())};
 }
 
 }  // namespace
@@ -727,33 +734,15 @@ extern "C" int sc_debug_attn_trace4(unsigned long long* host_out) {
 }
 #endif
 
-// returns 1 if the kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_bwd_ring8(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                      int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (dh != B4DH || L <= 224 || L > 257 || Lq != L || causal) return 0;
-    const int NBQ = L > 256 ? 9 : 8;
-    const int rows = NBQ == 9 ? 264 : 256;
-    const size_t lds = (size_t)2 * rows * dh * 2 + (size_t)256 * dh * 2 + (size_t)B4RING * B4NW * 2048 + (size_t)4 * rows * 4 +
-                       (size_t)B4NW * 128 * 4 + 512 + (size_t)B4NW * 64 * 4 + (NBQ == 9 ? (size_t)B4NW * 64 * 4 : 0) +
-                       (size_t)(2 * NBQ + 2) * 4 + 56;
-    const long long dqb = (long long)B * L * 3 * H * dh * 2;
-    if (dqb >= 0xFFFFFFF0ll) return 0;
-    if (lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int nheads = B * H;
-    int grid = nheads < ncu ? nheads : ncu;
-    if (const char* e = getenv("SC_ATTN_GRID")) { const int gcap = atoi(e); if (gcap > 0 && gcap < grid) grid = gcap; }   // measurement: fewer workgroups
+bool sc_attn_bwd_ring8_accepts(const AttnShape& s) { return bwd4_geom(s).ok; }
 
-    const float scale = 1.0f / sqrtf((float)dh);
-    const bf16 *q = (const bf16*)qkv, *o = (const bf16*)out, *g = (const bf16*)dout;
-    bf16* dq = (bf16*)dqkv;
-    if (NBQ == 9) launch_bwd4<9>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb);
-    else launch_bwd4<8>(grid, lds, st, q, o, g, lse, delta, dq, L, H, nheads, scale, (unsigned)dqb);
-    return 1;
+int sc_attn_bwd_ring8_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    const Bwd4Geom g = bwd4_geom(s);
+    const int grid = attn_grid_cap(attn_persistent_grid(s.nheads()));
+    if (!grid) return -1;
+    attn_dispatch(attn_vals<8, 9>{}, g.NBQ, [&](auto NBQ) {
+        attn_launch(attn_bwd4_kernel<NBQ.value>, grid, B4NW * 64, g.lds, st, o.qkv, o.out, o.dout, o.lse, o.delta, o.dqkv, s.L,
+                    s.H, s.nheads(), s.scale(), (unsigned)s.dqkv_bytes());
+    });
+    return 0;
 }

@@ -105,19 +105,13 @@ __global__ __launch_bounds__(256) void attn_bwd_cls_kernel(const bf16* __restric
 
 }  // namespace
 
-// returns 1 if this kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_bwd_cls(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                    int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (Lq != 1 || L < 2 || (dh != 64 && dh != 32 && dh != 80)) return 0;     // streams the keys: no bound on L
-    const float scale = 1.0f / sqrtf((float)dh);
-    if (dh == 64)
-        attn_bwd_cls_kernel<64><<<B * H, 256, 0, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                                                       (bf16*)dqkv, L, H, scale, causal);
-    else if (dh == 80)
-        attn_bwd_cls_kernel<80><<<B * H, 256, 0, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                                                       (bf16*)dqkv, L, H, scale, causal);
-    else
-        attn_bwd_cls_kernel<32><<<B * H, 256, 0, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                                                       (bf16*)dqkv, L, H, scale, causal);
-    return 1;
+// streams the keys: no bound on L
+bool sc_attn_bwd_cls_accepts(const AttnShape& s) { return s.Lq == 1 && s.L >= 2 && (s.dh == 64 || s.dh == 32 || s.dh == 80); }
+
+int sc_attn_bwd_cls_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    attn_dispatch(attn_vals<32, 80, 64>{}, s.dh, [&](auto DH) {
+        attn_launch(attn_bwd_cls_kernel<DH.value>, s.nheads(), 256, 0, st, o.qkv, o.out, o.dout, o.lse, o.delta, o.dqkv, s.L, s.H,
+                    s.scale(), s.causal);
+    });
+    return 0;
 }

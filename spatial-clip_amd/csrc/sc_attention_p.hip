@@ -25,7 +25,6 @@
 // raised priority: without s_setprio their DMA issue queues behind the compute waves' VALU (88 us).
 //   reference: nn.MultiheadAttention via src/open_clip/transformer.py:253,272-287; causal mask :1080-1086.
 #include "sc_attn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -248,60 +247,30 @@ __global__ __launch_bounds__(1024) void attn_fwd_p_kernel(const bf16* __restrict
     }
 }
 
-template <typename K>
-void set_lds_p(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-template <int NB>
-void launch_fwd_p(bool causal, int grid, int nthreads, size_t lds, hipStream_t st, const bf16* qkv, bf16* out, float* lse,
-                  int L, int Lq, int H, int nheads, float scale, unsigned ob, unsigned lb) {
-
-    if (causal) {
-        set_lds_p(attn_fwd_p_kernel<NB, true>, lds);
-        attn_fwd_p_kernel<NB, true><<<grid, nthreads, lds, st>>>(qkv, out, lse, L, Lq, H, nheads, scale, ob, lb);
-    } else {
-        set_lds_p(attn_fwd_p_kernel<NB, false>, lds);
-        attn_fwd_p_kernel<NB, false><<<grid, nthreads, lds, st>>>(qkv, out, lse, L, Lq, H, nheads, scale, ob, lb);
-    }
+// one compute wave per 16-query tile + the loader waves; K / V double-buffered, one Q slot and one O strip per tile
+struct FwdPGeom {
+    int NB, threads;
+    size_t lds;
+    bool ok;
+};
+FwdPGeom fwd_p_geom(const AttnShape& s) {
+    const int NB = (s.L + 31) / 32, nqt = (s.Lq + 15) / 16;
+    const size_t lds = (size_t)4 * NB * 32 * PDH * 2 + (size_t)nqt * QSLOT + 64 + (size_t)nqt * 1024;   // images, Q slots, counter, O strips
+    return {NB, (nqt + NLOAD) * 64, lds,
+            s.dh == PDH && s.L <= 224 && nqt + NLOAD <= 16 && lds <= ATTN_LDS_MAX && attn_fits_buffer(s.out_bytes())};
 }
 
 }  // namespace
 
-// returns 1 if the persistent kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_fwd_persistent(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                           hipStream_t st) {
-    if (dh != PDH || L > 224) return 0;
-    const int NB = (L + 31) / 32;
-    const int nqt = (Lq + 15) / 16;
-    const long long ob = (long long)B * L * H * dh * 2, lb = (long long)B * H * L * 4;
-    if (ob >= 0xFFFFFFF0ll) return 0;
-    const int nheads = B * H;
-    if (nqt + NLOAD > 16) return 0;
-    const int nwaves = nqt + NLOAD;                         // one compute wave per query tile + the loader waves
-    const size_t lds = (size_t)4 * NB * 32 * dh * 2 + (size_t)nqt * QSLOT + 64 + (size_t)nqt * 1024;   // images, Q slots, counter, O strips
-    if (lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int grid = nheads < ncu ? nheads : ncu;
-    const float scale = 1.0f / sqrtf((float)dh);
-    const bf16* q = (const bf16*)qkv;
-    bf16* o = (bf16*)out;
-    const int nt = nwaves * 64;
-    switch (NB) {
-        case 1: launch_fwd_p<1>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 2: launch_fwd_p<2>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 3: launch_fwd_p<3>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 4: launch_fwd_p<4>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 5: launch_fwd_p<5>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 6: launch_fwd_p<6>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        case 7: launch_fwd_p<7>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb); break;
-        default: return 0;
-    }
-    return 1;
+bool sc_attn_fwd_persistent_accepts(const AttnShape& s) { return fwd_p_geom(s).ok; }
+
+int sc_attn_fwd_persistent_launch(const AttnShape& s, const AttnFwdOps& o, hipStream_t st) {
+    const FwdPGeom g = fwd_p_geom(s);
+    const int grid = attn_persistent_grid(s.nheads());
+    if (!grid) return -1;
+    attn_dispatch(attn_blocks7{}, g.NB, attn_causal{}, s.causal != 0, [&](auto NB, auto C) {
+        attn_launch(attn_fwd_p_kernel<NB.value, C.value != 0>, grid, g.threads, g.lds, st, o.qkv, o.out, o.lse, s.L, s.Lq, s.H,
+                    s.nheads(), s.scale(), (unsigned)s.out_bytes(), (unsigned)s.lse_bytes());
+    });
+    return 0;
 }

@@ -19,7 +19,6 @@
 // store}.  Every wait is on a counter that is bumped by waves that do not wait for the waiter in between (loaders bump
 // `vready` before they look at `arrive`; compute waves bump `arrive` before they look at `vready`).
 #include "sc_attn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -220,48 +219,31 @@ __global__ __launch_bounds__(768) void attn_fwd_p2_kernel(const bf16* __restrict
     }
 }
 
-template <int NB>
-void launch_fwd_p2(bool causal, int grid, int nthreads, size_t lds, hipStream_t st, const bf16* qkv, bf16* out, float* lse,
-                   int L, int Lq, int H, int nheads, float scale, unsigned ob, unsigned lb) {
-    if (causal) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_p2_kernel<NB, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attn_fwd_p2_kernel<NB, true><<<grid, nthreads, lds, st>>>(qkv, out, lse, L, Lq, H, nheads, scale, ob, lb);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_p2_kernel<NB, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attn_fwd_p2_kernel<NB, false><<<grid, nthreads, lds, st>>>(qkv, out, lse, L, Lq, H, nheads, scale, ob, lb);
-    }
+// a compute wave owns two 16-query tiles; K double-buffered, one V image, one Q slot per tile, one O strip per wave
+struct FwdP2Geom {
+    int NB, threads;
+    size_t lds;
+    bool ok;
+};
+FwdP2Geom fwd_p2_geom(const AttnShape& s) {
+    const int NB = (s.L + 31) / 32, nqt = (s.Lq + 15) / 16, ncomp = (nqt + 1) / 2;
+    const size_t lds = (size_t)3 * NB * 32 * P2DH * 2 + (size_t)nqt * P2QSLOT + 64 + (size_t)ncomp * 1024;
+    return {NB, (ncomp + P2NLOAD) * 64, lds,
+            s.dh == P2DH && s.L > 224 && s.L <= 288 && ncomp + P2NLOAD <= 12 && lds <= ATTN_LDS_MAX &&
+                attn_fits_buffer(s.out_bytes())};
 }
 
 }  // namespace
 
-// returns 1 if the kernel took the launch, 0 if the shape is outside its range (caller falls back)
-int sc_attn_fwd_persistent2(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                            hipStream_t st) {
-    if (dh != P2DH || L <= 224 || L > 288 || Lq < 1 || Lq > L) return 0;
-    const int NB = (L + 31) / 32;                            // 8 or 9
-    const int nqt = (Lq + 15) / 16;
-    const int ncomp = (nqt + 1) / 2;
-    if (ncomp + P2NLOAD > 12) return 0;
-    const long long ob = (long long)B * L * H * dh * 2, lb = (long long)B * H * L * 4;
-    if (ob >= 0xFFFFFFF0ll) return 0;
-    const size_t lds = (size_t)3 * NB * 32 * dh * 2 + (size_t)nqt * P2QSLOT + 64 + (size_t)ncomp * 1024;
-    if (lds > 160 * 1024) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
-        ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    const int nheads = B * H;
-    const int grid = nheads < ncu ? nheads : ncu;
-    const float scale = 1.0f / sqrtf((float)dh);
-    const int nt = (ncomp + P2NLOAD) * 64;
-    const bf16* q = (const bf16*)qkv;
-    bf16* o = (bf16*)out;
-    if (NB == 8) launch_fwd_p2<8>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb);
-    else launch_fwd_p2<9>(causal, grid, nt, lds, st, q, o, lse, L, Lq, H, nheads, scale, (unsigned)ob, (unsigned)lb);
-    return 1;
+bool sc_attn_fwd_persistent2_accepts(const AttnShape& s) { return fwd_p2_geom(s).ok; }
+
+int sc_attn_fwd_persistent2_launch(const AttnShape& s, const AttnFwdOps& o, hipStream_t st) {
+    const FwdP2Geom g = fwd_p2_geom(s);
+    const int grid = attn_persistent_grid(s.nheads());
+    if (!grid) return -1;
+    attn_dispatch(attn_vals<9, 8>{}, g.NB, attn_causal{}, s.causal != 0, [&](auto NB, auto C) {
+        attn_launch(attn_fwd_p2_kernel<NB.value, C.value != 0>, grid, g.threads, g.lds, st, o.qkv, o.out, o.lse, s.L, s.Lq, s.H,
+                    s.nheads(), s.scale(), (unsigned)s.out_bytes(), (unsigned)s.lse_bytes());
+    });
+    return 0;
 }

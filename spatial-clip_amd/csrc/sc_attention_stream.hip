@@ -566,50 +566,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // the instances that exist: (64, non-causal) at any L, (80, either) up to MAXL
-bool stream_shape(int B, int L, int Lq, int H, int dh, int causal) {
-    if (B <= 0 || H <= 0 || L <= 0 || Lq <= 0 || Lq > L) return false;
-    return dh == 64 ? !causal : dh == 80 && L <= MAXL;
+bool stream_shape(const AttnShape& s) { return s.dh == 64 ? !s.causal : s.dh == 80 && s.L <= MAXL; }
+
+template <class F>
+void stream_instance(const AttnShape& s, F&& f) {
+    if (s.dh == 64) f(std::integral_constant<int, 64>{}, std::false_type{});
+    else attn_dispatch(attn_causal{}, s.causal != 0, [&](auto C) { f(std::integral_constant<int, 80>{}, C); });
 }
 
 // number of workgroups for `rows` rows in blocks of `per`, or 0 when it does not fit a grid
-unsigned stream_grid(int B, int H, int rows, int per) {
-    const long long g = (long long)B * H * ((rows + per - 1) / per);
+unsigned stream_grid(const AttnShape& s, int rows, int per) {
+    const long long g = (long long)s.B * s.H * ((rows + per - 1) / per);
     return g > 0x7fffffffLL ? 0u : (unsigned)g;
 }
-
-template <int DH, bool CAUSAL>
-int launch_fwd(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, hipStream_t st) {
-    const unsigned grid = stream_grid(B, H, Lq, LB);
-    if (!grid) return 0;
-    attn_fwd_stream_kernel<DH, CAUSAL><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)out, lse, L, Lq, H, Head<DH>::SCALE);
-    return 1;
-}
-
-template <int DH, bool CAUSAL>
-int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B, int L,
-               int Lq, int H, hipStream_t st) {
-    const unsigned grid = stream_grid(B, H, L, LB), gkv = stream_grid(B, H, L, Head<DH>::DKV_KEYS);
-    if (!grid || !gkv) return 0;
-    attn_bwd_dq_stream_kernel<DH, CAUSAL><<<grid, 256, 0, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
-                                                                delta, (bf16*)dqkv, L, Lq, H, Head<DH>::SCALE);
-    attn_bwd_dkv_stream_kernel<DH, CAUSAL><<<gkv, 256, 0, st>>>((const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv,
-                                                                L, Lq, H, Head<DH>::SCALE);
-    return 1;
+unsigned stream_grid_dkv(const AttnShape& s) {
+    return stream_grid(s, s.L, s.dh == 64 ? Head<64>::DKV_KEYS : Head<80>::DKV_KEYS);
 }
 
 }  // namespace
 
-int sc_attn_fwd_stream(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                       hipStream_t st) {
-    if (!stream_shape(B, L, Lq, H, dh, causal)) return 0;
-    if (dh == 64) return launch_fwd<64, false>(qkv, out, lse, B, L, Lq, H, st);
-    return causal ? launch_fwd<80, true>(qkv, out, lse, B, L, Lq, H, st) : launch_fwd<80, false>(qkv, out, lse, B, L, Lq, H, st);
+bool sc_attn_fwd_stream_accepts(const AttnShape& s) { return stream_shape(s) && stream_grid(s, s.Lq, LB); }
+
+int sc_attn_fwd_stream_launch(const AttnShape& s, const AttnFwdOps& o, hipStream_t st) {
+    stream_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_fwd_stream_kernel<DH.value, C.value != 0>, stream_grid(s, s.Lq, LB), 256, 0, st, o.qkv, o.out, o.lse,
+                    s.L, s.Lq, s.H, Head<DH.value>::SCALE);
+    });
+    return 0;
 }
 
-int sc_attn_bwd_stream(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                       int B, int L, int Lq, int H, int dh, int causal, hipStream_t st) {
-    if (!stream_shape(B, L, Lq, H, dh, causal)) return 0;
-    if (dh == 64) return launch_bwd<64, false>(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, st);
-    return causal ? launch_bwd<80, true>(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, st)
-                  : launch_bwd<80, false>(qkv, out, dout, lse, delta, dqkv, B, L, Lq, H, st);
+bool sc_attn_bwd_stream_accepts(const AttnShape& s) { return stream_shape(s) && stream_grid(s, s.L, LB) && stream_grid_dkv(s); }
+
+int sc_attn_bwd_stream_launch(const AttnShape& s, const AttnBwdOps& o, hipStream_t st) {
+    stream_instance(s, [&](auto DH, auto C) {
+        attn_launch(attn_bwd_dq_stream_kernel<DH.value, C.value != 0>, stream_grid(s, s.L, LB), 256, 0, st, o.qkv, o.out,
+                    o.dout, o.lse, o.delta, o.dqkv, s.L, s.Lq, s.H, Head<DH.value>::SCALE);
+        attn_launch(attn_bwd_dkv_stream_kernel<DH.value, C.value != 0>, stream_grid_dkv(s), 256, 0, st, o.qkv, o.dout, o.lse,
+                    o.delta, o.dqkv, s.L, s.Lq, s.H, Head<DH.value>::SCALE);
+    });
+    return 0;
 }

@@ -3,45 +3,7 @@
 // reads (ds_read_b128) and transposed reads (ds_read_b64_tr_b16), fragment accessors, quad reductions by
 // v_permlane16/32_swap, raw v_exp_f32.
 #pragma once
-#include "sc_common.h"
-#include "sc_kernels.h"
-
-// sc_attention_p.hip: persistent LDS-DMA forward; returns 1 when it took the launch, 0 when the shape is out of its range
-int sc_attn_fwd_persistent(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                           hipStream_t st);
-
-// sc_attention_p2.hip (round 5): the same for 224 < L <= 288 (ViT-L/14's 257 tokens): two query tiles per compute wave, one V image
-int sc_attn_fwd_persistent2(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                            hipStream_t st);
-
-// sc_attention_bwd1.hip: single-pass backward (dQ accumulated in LDS); 1 = launched, 0 = shape out of range
-int sc_attn_bwd_single_pass(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                            int B, int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_bwd3.hip (round 4): single pass, dQ by MFMA chains over a ring of dS tiles, rolling Q / dO refill; 1 = launched
-int sc_attn_bwd_ring(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                     int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_bwd4.hip (round 5): the ring design for 224 < L <= 257 (eight key waves, no helper wave, the 257th key as
-// rank-one terms in the reducers); 1 = launched
-int sc_attn_bwd_ring8(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                      int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_bwd2.hip: persistent two-pass backward with loader waves; 1 = launched, 0 = shape out of range
-int sc_attn_bwd_persistent(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                           int B, int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_cls.hip: backward for q_rows == 1 (class-token-only last block); 1 = launched, 0 = not this shape
-int sc_attn_bwd_cls(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-                    int L, int Lq, int H, int dh, int causal, hipStream_t st);
-
-// sc_attention_stream.hip: K / V (Q / dO) streamed through LDS in 64-row tiles.  dh = 64, non-causal, any L (dispatched
-// above MAXL tokens, or at any L with SC_ATTN_LONG=1) and dh = 80 (ViT-H), 0 < L <= MAXL, causal or not; 1 = launched,
-// 0 = shape out of range
-int sc_attn_fwd_stream(const void* qkv, void* out, float* lse, int B, int L, int Lq, int H, int dh, int causal,
-                       hipStream_t st);
-int sc_attn_bwd_stream(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                       int B, int L, int Lq, int H, int dh, int causal, hipStream_t st);
+#include "sc_attn_host.h"
 
 namespace {
 

@@ -12,3 +12,8 @@ enum sc_attn_path {
     SC_ATTN_BWD_CLS = 0, SC_ATTN_BWD_RING, SC_ATTN_BWD_RING8, SC_ATTN_BWD_SINGLE_PASS, SC_ATTN_BWD_PERSISTENT,
     SC_ATTN_BWD_FUSED, SC_ATTN_BWD_DQ_DKV, SC_ATTN_BWD_STREAM
 };
+
+// Debug exports (not in the public header).  sc_debug_attn_plan: the paths the next sc_attn_fwd / sc_attn_bwd of this shape would
+// take under the current environment switches; -1 with sc_attn_fwd's own message for a shape they refuse.  No HIP call.
+extern "C" int sc_debug_attn_last_path(int* fwd, int* bwd);
+extern "C" int sc_debug_attn_plan(int B, int L, int H, int dh, int causal, int q_rows, int* fwd, int* bwd);

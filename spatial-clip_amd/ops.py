@@ -218,6 +218,17 @@ def attn_last_path():
     return (ATTN_FWD_PATHS[f.value] if f.value >= 0 else "none", ATTN_BWD_PATHS[b.value] if b.value >= 0 else "none")
 
 
+def attn_plan(B: int, L: int, H: int, dh: int, causal: bool = False, q_rows: int = 0):
+    """(forward, backward): the names of the kernels that ``attn_fwd`` / ``attn_bwd`` would dispatch this shape to under the
+    current environment switches, without launching anything (``sc_debug_attn_plan``: host arithmetic only, so it runs
+    without a GPU).  A shape the library refuses raises RuntimeError with ``sc_attn_fwd``'s own message."""
+    fn = getattr(_lib.lib(), "sc_debug_attn_plan")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)] * 2
+    f, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    check(fn(B, L, H, dh, int(causal), q_rows, ctypes.byref(f), ctypes.byref(b)), "sc_debug_attn_plan")
+    return ATTN_FWD_PATHS[f.value], ATTN_BWD_PATHS[b.value]
+
+
 # ------------------------------------------------------------------------------------------ norms
 def _t8_args(t8, rows: int, d: int, what: str):
     """(buffer uint8 [rows, >= d], scale fp32 [1], amax fp32 [64]) -> ctypes arguments of a per-tensor e4m3 second output."""

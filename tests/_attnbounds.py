@@ -44,7 +44,7 @@ BOUNDARY_LENGTHS = [2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 77, 197, 223, 224, 22
 STREAM_LONG_LENGTHS = (list(range(321, 331)) + [383, 384, 385, 447, 448, 449, 511, 512, 513, 575, 576, 577, 578, 640, 785,
                                                 1023, 1024, 1025, 1370])
 FAMILIES = ("diffuse", "mixed", "peaked")
-MAXL = 320                                            # sc_attn_common.h:48
+MAXL = 320                                            # sc_attn_common.h:10
 
 
 def q_rows_at(L: int):

@@ -8,24 +8,14 @@ collected before the assertion.  Inside a path's accepted range every length run
 the boundary lengths run (the fallback, by name).  q_rows in {1, 15, 16, 17, L - 1} runs at the boundary lengths (``mixed``
 family) on every path, accepted or declined.  The backward kernels get the model's forward results (see _attnbounds).
 
-``expected_fwd`` / ``expected_bwd`` restate the dispatcher's predicates (file:line beside each)."""
+``expected_fwd`` / ``expected_bwd`` (tests/_attnpaths.py) restate the dispatcher's predicates (file:line beside each)."""
 import pytest
 import torch
 
 from tests import _attnbounds as A
+from tests._attnpaths import BWD_ENV, DEFAULT, FWD_ENV, SWITCHES, expected_bwd, expected_fwd, fused_fits
 
 pytestmark = pytest.mark.gpu
-
-SWITCHES = ("SC_ATTN_PERSIST", "SC_ATTN_PERSIST2", "SC_ATTN_LONG", "SC_ATTN_BWD3", "SC_ATTN_BWD4", "SC_ATTN_BWD1",
-            "SC_ATTN_BWD2", "SC_ATTN_FUSED")
-DEFAULT = {"SC_ATTN_PERSIST": "1", "SC_ATTN_PERSIST2": "1", "SC_ATTN_LONG": "0", "SC_ATTN_BWD3": "1", "SC_ATTN_BWD4": "1",
-           "SC_ATTN_BWD1": "1", "SC_ATTN_BWD2": "1", "SC_ATTN_FUSED": "1"}
-_NO_BWD = {"SC_ATTN_BWD3": "0", "SC_ATTN_BWD4": "0", "SC_ATTN_BWD1": "0", "SC_ATTN_BWD2": "0"}
-FWD_ENV = {"persistent": {"SC_ATTN_PERSIST2": "0"}, "persistent2": {}, "per_head": {"SC_ATTN_PERSIST": "0"},
-           "stream": {"SC_ATTN_LONG": "1"}}
-BWD_ENV = {"ring": {**_NO_BWD, "SC_ATTN_BWD3": "1"}, "ring8": {**_NO_BWD, "SC_ATTN_BWD4": "1"},
-           "single_pass": {**_NO_BWD, "SC_ATTN_BWD1": "1"}, "persistent": {**_NO_BWD, "SC_ATTN_BWD2": "1"},
-           "fused": dict(_NO_BWD), "dq_dkv": {**_NO_BWD, "SC_ATTN_FUSED": "0"}, "stream": {"SC_ATTN_LONG": "1"}, "cls": {}}
 
 
 def _ops():
@@ -40,53 +30,6 @@ def _few_threads():
     torch.set_num_threads(min(n, 4))          # the CPU references work on [6, L, L] operands
     yield
     torch.set_num_threads(n)
-
-
-# ---------------------------------------------------------------------------------------------------------- the dispatcher, restated
-def _streams(env, dh, L, causal):
-    """attn_stream (sc_attention.hip:497-504): head dim 80 up to MAXL; head dim 64 non-causal above MAXL or with SC_ATTN_LONG=1."""
-    if dh == 80:
-        return L <= A.MAXL
-    return dh == 64 and not causal and (L > A.MAXL or env["SC_ATTN_LONG"] == "1")
-
-
-def expected_fwd(env, dh, L, causal, nq):
-    if _streams(env, dh, L, causal):
-        return "stream"
-    on = env["SC_ATTN_PERSIST"] != "0"
-    # sc_attention_p.hip:274-280: dh 64, L <= 224, one compute wave per 16-query tile beside 3 loader waves, 16 waves at most
-    if on and dh == 64 and L <= 224 and (nq + 15) // 16 + 3 <= 16:
-        return "persistent"
-    # sc_attention_p2.hip:242-246: 224 < L <= 288 (one compute wave per two query tiles: always within its 12 waves)
-    if on and env["SC_ATTN_PERSIST2"] != "0" and dh == 64 and 224 < L <= 288:
-        return "persistent2"
-    return "per_head"
-
-
-def fused_fits(dh, L):
-    """sc_attention.hip, lds_fused: Q, K, V, dO images of Lp = L rounded up to 32 rows plus two fp32 row vectors in 160 KiB."""
-    Lp = (L + 31) & ~31
-    return 4 * Lp * dh * 2 + 2 * Lp * 4 <= 160 * 1024
-
-
-def expected_bwd(env, dh, L, causal, nq):
-    cls = nq == 1 and L >= 2                                             # sc_attention_cls.hip:111
-    if _streams(env, dh, L, causal):
-        return "cls" if cls else "stream"
-    if cls:
-        return "cls"
-    full64 = dh == 64 and nq == L
-    if env["SC_ATTN_BWD3"] != "0" and full64 and L <= 224 and not causal:            # sc_attention_bwd3.hip:395
-        return "ring"
-    if env["SC_ATTN_BWD4"] != "0" and full64 and 224 < L <= 257 and not causal:      # sc_attention_bwd4.hip:733
-        return "ring8"
-    if env["SC_ATTN_BWD1"] != "0" and full64 and L <= 224 and not causal:            # sc_attention_bwd1.hip:371
-        return "single_pass"
-    if env["SC_ATTN_BWD2"] != "0" and full64 and L <= 224:                           # sc_attention_bwd2.hip:364-366
-        return "persistent"
-    if env["SC_ATTN_FUSED"] != "0" and fused_fits(dh, L):
-        return "fused"
-    return "dq_dkv"
 
 
 def test_fused_backward_stops_at_288_tokens_at_head_dim_64():
