@@ -19,6 +19,10 @@
 //          retires its reads one barrier later than the leading group).
 //   Epilogue: bf16 outputs without an extra input tile take a bf16 LDS strip (epilogue_bf16_lds); the others the
 //   fp32 LDS staging shared with sc_gemm256.hip (sc_gemm_common.h).
+//
+//   Tail split (non-persistent kernel, splitk == 1): the tiles of a launch's partial last round run as HALF TILES of 128 rows
+//   (half_tile below: two phases and three images per K tile, nine-slot ring -- the same two rules, derived there), one per
+//   CU, so the round costs a half tile's time.  Which launches: sc_debug_gemm_tail_rule / sc_tail_default at the launcher.
 #include "sc_gemm_common.h"
 #include <stdlib.h>
 #include <map>
@@ -47,8 +51,9 @@ SC_DEVICE void dma16(const void* src, char* lds_wave_base) {
 // XOR-swizzled by row so the 8-B writes (2-way at worst) and 16-B reads spread over the banks.
 //   BF16 / BF16_BIAS: C = bf16(acc (+ bias));  GELU_PAIR: C = u = bf16(acc + bias), C2 = bf16(gelu(float(u)));
 //   GELU_GRAD_PAIR: C = bf16(gelu'(float(u))), C2 as before, u itself is not stored.
-template <int EPI, bool Q8 = false, bool LUT = false>
-SC_DEVICE void epilogue_bf16_lds(f32x4 (&acc)[8][4], const GemmArgs& g, char* strip, int row0, int col0, int lane,
+// NI = 16-row accumulator blocks of the wave tile: 8 (128 rows, four passes) or 4 (the 64 rows of a half tile, two passes).
+template <int EPI, bool Q8 = false, bool LUT = false, int NI = 8>
+SC_DEVICE void epilogue_bf16_lds(f32x4 (&acc)[NI][4], const GemmArgs& g, char* strip, int row0, int col0, int lane,
                                  const unsigned* lut = nullptr) {
     float amax_lane = 0.f;
     const float q8s = (Q8 && sc_epi_gelu_fwd(EPI) && g.q8) ? *g.q8_scale : 0.f;
@@ -66,7 +71,7 @@ SC_DEVICE void epilogue_bf16_lds(f32x4 (&acc)[8][4], const GemmArgs& g, char* st
     const int rr = lane >> 3, rc = lane & 7;                      // read side: row (+ 8 s), 16-B chunk
     const int gcol = col0 + rc * 8;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
+    for (int p = 0; p < NI / 2; ++p) {
 #pragma unroll
         for (int ib = 0; ib < 2; ++ib) {
             const int r = ib * 16 + li;                           // strip row
@@ -223,16 +228,206 @@ SC_DEVICE void ktile(char* smem, const Stager& S, int t, const int (&a_off)[2], 
     phase<D, 4>(smem, S, t, a_off, b_off, a, b0, b1, acc);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Half tile (128 rows x 256 columns): the workgroups of a launch's partial last round (GemmArgs::tail_first).
+// Half h of tile (tm, tn) is rows tm 256 + 128 h + [0, 128).  Same 2 x 4 wave layout; wave (wr, wc) owns 64 x 64 -- what the full
+// tile calls quadrants (0,0) and (0,1): acc[0..3][*] over the images A0', B0, B1, where A0' holds the half tile's 128 rows
+// (M-wave wr: rows [64 wr, 64 wr + 64)) and B0 / B1 are the full tile's.  A K tile is two phases (the full tile's phases 1
+// and 2, same fragment reads, same 16 MFMAs in the same order, so every output element sees the same sums) over THREE images.
+//
+// Schedule, in the terms of the RAW / WAR rules of the file header.  Number the phases 2 t (PH 1) and 2 t + 1 (PH 2) of K tile t.
+//   reads:  A0'(t), B0(t) in phase 2 t;  B1(t) in phase 2 t + 1.
+//   ring:   R K tiles x 3 images; image x(t + R) takes the slot of x(t).
+//   WAR:    x(t + R) may be issued two phases after x(t) was read:  A0' / B0 (t + R) from phase 2 t + 2, B1(t + R) from 2 t + 3.
+//           So the issue-to-read distance is 2 R - 2 phases whatever the order: R = 3 (nine slots, 144 KiB -- R = 4 does not
+//           fit in 160 KiB) gives four phases = two K tiles, against the full tile's six phases with its 8-slot ring.
+//   issue:  PH 1 of K tile t stages A0'(t + 2) and B0(t + 2) (two DMA pairs), PH 2 stages B1(t + 2) (one pair): each exactly
+//           two phases after the read of the slot's previous image, the earliest the WAR rule allows.
+//   RAW:    per-lane issue order is ... B1(t) | A0' B0 (t+1) | B1(t+1) | A0' B0 (t+2) | B1(t+2) ...
+//           PH 1 (t) must retire B1(t), read in the next phase: 5 younger images = vmcnt(10);
+//           PH 2 (t) must retire A0' B0 (t+1): 4 younger images (B1(t+1), A0' B0 (t+2), B1(t+2)) = vmcnt(8).
+//           A phase that stages nothing (t + 2 >= nt: the ring drains) waits for vmcnt(0), as in the full tile.
+//   prologue: K tiles 0 and 1 whole (six images); A0' B0 (0) have landed at vmcnt(8) (vmcnt(0) when nt == 1), and PH 1 (0)
+//           then finds exactly the steady-state queue.
+// The two wave groups stay staggered by one barrier; a half tile passes 4 nt + 2 (+ 1 for the trailing group) barriers.
+constexpr int HRING = 9 * HALF;                     // 144 KiB
+constexpr int hslot(int D, int q) { return (D * 3 + q) * HALF; }      // q: 0 A0', 1 B0, 2 B1 of the K tile with t % 3 == D
+
+struct HStager {
+    const bf16* src[3][2];
+    int nt;
+    int wave;
+};
+
+template <int D, int PH>
+SC_DEVICE void hphase(char* smem, const HStager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
+                      bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[4][4]) {
+    if (PH == 1) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                b0[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 1) + b_off[kk] + jj * 2048);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii)
+                a[kk * 4 + ii] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 0) + a_off[kk] + ii * 2048);
+    } else {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                b1[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 2) + b_off[kk] + jj * 2048);
+    }
+    constexpr int DS = (D + 2) % 3;
+    const int ts = t + 2;
+    if (ts < S.nt) {
+        if (PH == 1) {
+            dma16(S.src[0][0] + (size_t)ts * BK, smem + hslot(DS, 0) + S.wave * 1024);
+            dma16(S.src[0][1] + (size_t)ts * BK, smem + hslot(DS, 0) + (8 + S.wave) * 1024);
+            dma16(S.src[1][0] + (size_t)ts * BK, smem + hslot(DS, 1) + S.wave * 1024);
+            dma16(S.src[1][1] + (size_t)ts * BK, smem + hslot(DS, 1) + (8 + S.wave) * 1024);
+            asm volatile("s_waitcnt vmcnt(10)" ::: "memory");     // retires B1(t), read in the NEXT phase
+        } else {
+            dma16(S.src[2][0] + (size_t)ts * BK, smem + hslot(DS, 2) + S.wave * 1024);
+            dma16(S.src[2][1] + (size_t)ts * BK, smem + hslot(DS, 2) + (8 + S.wave) * 1024);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // retires A0', B0 of K tile t + 1
+        }
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    constexpr int nj = PH - 1;
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                acc[ii][nj * 2 + jj] = sc_mfma16(nj ? b1[kk * 2 + jj] : b0[kk * 2 + jj], a[kk * 4 + ii], acc[ii][nj * 2 + jj]);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int D>
+SC_DEVICE void hktile(char* smem, const HStager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
+                      bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[4][4]) {
+    hphase<D, 1>(smem, S, t, a_off, b_off, a, b0, b1, acc);
+    hphase<D, 2>(smem, S, t, a_off, b_off, a, b0, b1, acc);
+}
+
+// rows [mh, mh + 128) x columns [n0, n0 + 256) of the product (splitk == 1); the caller has checked mh < g.M
 template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const int li = lane & 15, lg = lane >> 4;
 
-    int idx = sc_xcd_remap(blockIdx.x, gridDim.x);
+    HStager S;
+    S.nt = g.K / BK;
+    S.wave = wave;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int r = (p * 8 + wave) * 8 + (lane >> 3);          // row of the image, 128 B per row
+        const int lc = (lane & 7) ^ ((r >> 1) & 7);
+        const int ga = min(mh + r, g.M - 1);
+        S.src[0][p] = g.A + (size_t)ga * g.lda + lc * 8;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int gb = min(n0 + (r >> 5) * 64 + h * 32 + (r & 31), g.N - 1);
+            S.src[1 + h][p] = g.B + (size_t)gb * g.ldb + lc * 8;
+        }
+    }
+    int a_off[2], b_off[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const int coff = ((kk * 4 + lg) ^ ((li >> 1) & 7)) << 4;
+        a_off[kk] = (wr * 64 + li) * 128 + coff;
+        b_off[kk] = (wc * 32 + li) * 128 + coff;
+    }
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // prologue: K tiles 0 and 1 (six images)
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const int ts = s / 3, q = s % 3;
+        if (ts < S.nt) {
+            dma16(S.src[q][0] + (size_t)ts * BK, smem + hslot(ts, q) + wave * 1024);
+            dma16(S.src[q][1] + (size_t)ts * BK, smem + hslot(ts, q) + (8 + wave) * 1024);
+        }
+    }
+    if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
+    __builtin_amdgcn_sched_barrier(0);
+
+    bf16x8 a[8], b0[4], b1[4];
+    for (int kt = 0; kt < S.nt; kt += 3) {
+        hktile<0>(smem, S, kt, a_off, b_off, a, b0, b1, acc);
+        if (kt + 1 < S.nt) hktile<1>(smem, S, kt + 1, a_off, b_off, a, b0, b1, acc);
+        if (kt + 2 < S.nt) hktile<2>(smem, S, kt + 2, a_off, b_off, a, b0, b1, acc);
+    }
+    if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+
+    // the full tile's epilogues on a 64-row wave tile: two strip passes / one fp32 staging block
+    const int row0 = mh + wr * 64, col0 = n0 + wc * 64;
+    if (EPI == SC_EPI_GELU_GRAD_PAIR && g.gelu_lut != nullptr) {
+        unsigned* lut = reinterpret_cast<unsigned*>(smem + 8 * 4096);
+        for (int c = t; c < SC_GELU_LUT_N / 4; c += 512)
+            reinterpret_cast<u32x4*>(lut)[c] = reinterpret_cast<const u32x4*>(g.gelu_lut)[c];
+        __syncthreads();
+        epilogue_bf16_lds<EPI, false, true>(acc, g, smem + wave * 4096, row0, col0, lane, lut);
+    } else if (EPI == SC_EPI_BF16 || EPI == SC_EPI_BF16_BIAS || sc_epi_gelu_fwd(EPI)) {
+        epilogue_bf16_lds<EPI>(acc, g, smem + wave * 4096, row0, col0, lane);
+    } else {
+        float* ep = reinterpret_cast<float*>(smem) + wave * 64 * SC_EPI_LD;
+        EpiRegs<EPI> er;
+        sc_epi_load<EPI>(er, row0, col0, lane, g, 64);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sc_epi_put(ep, i, j, li, lg, acc[i][j]);
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        sc_epilogue_store<EPI>(ep, er, row0, col0, lane, g, 0, -1, 64);
+    }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // Tail split (sc_gemm8p_try): workgroups [0, tail_first) compute the first tail_first tiles of the walk as full tiles, XCD
+    // remap over those alone; the last 2 tail_rem workgroups compute the remaining tail_rem tiles as half tiles.  Their own
+    // XCD remap gives an XCD a contiguous run of (tile, half) pairs, so the two halves of a tile share their B panel in one L2.
+    int idx, hh = -1;
+    if (g.tail_first > 0) {
+        const int b = (int)blockIdx.x - g.tail_first;
+        if (b >= 0) {
+            const int r = sc_xcd_remap(b, 2 * g.tail_rem);
+            idx = g.tail_first + (r >> 1);
+            hh = r & 1;
+        } else {
+            idx = sc_xcd_remap(blockIdx.x, g.tail_first);
+        }
+    } else {
+        idx = sc_xcd_remap(blockIdx.x, gridDim.x);
+    }
     int tn, tm, z;
     if (g.col_group > 0) {                                       // column-group walk (splitk == 1): sc_gemm_common.h
         sc_tile_colgroup(idx, g, tm, tn);
@@ -243,6 +438,17 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
         tm = idx % g.ntm;
         z = idx / g.ntm;
     }
+    if (hh >= 0) {                                               // workgroup-uniform: every wave takes the same path
+        const int mh = tm * BM + hh * 128;
+        if (mh < g.M) half_tile<EPI>(g, smem, mh, tn * BN);      // second half of a ragged last tile row: nothing to do
+        return;
+    }
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int wr = wave >> 2, wc = wave & 3;
+    const int li = lane & 15, lg = lane >> 4;
+
     const int m0 = tm * BM, n0 = tn * BN;
     const int kbeg = z * g.k_per_split;
     const int kend = min(g.K, kbeg + g.k_per_split);
@@ -350,10 +556,12 @@ int launch(const GemmArgs& g, int nblocks, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES > HRING ? LDS_BYTES : HRING);
         attr_done = true;
     }
-    gemm8p_kernel<EPI><<<nblocks, 512, LDS_BYTES, st>>>(g);
+    // a launch with half tiles needs their nine-slot ring
+    const int lds = (g.tail_first > 0 && HRING > LDS_BYTES) ? HRING : LDS_BYTES;
+    gemm8p_kernel<EPI><<<nblocks, 512, lds, st>>>(g);
     SC_LAUNCH_CHECK();
     return 1;
 }
@@ -1404,6 +1612,51 @@ static int sc_colgroup_default(int epi, const GemmArgs& g) {
     return 0;
 }
 
+// Tail split of the non-persistent NT kernel.  T tiles on S workgroup slots (one 140-KiB workgroup per CU) run in ceil(T / S)
+// rounds, and the last one keeps only rem = T % S of the S CUs busy.  When rem <= S / 2 those rem tiles are launched as 2 rem
+// half tiles (128 rows each, dispatched last), one per CU: the last round then costs a half tile's time instead of a tile's.
+// With more than S / 2 tiles in the last round the halves would not all find a free CU at once; with T <= S there is one round.
+extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem) {
+    const int r = (S > 0 && T > S) ? T % S : 0;
+    const bool split = r > 0 && 2 * r <= S;
+    if (nfull) *nfull = split ? T - r : T;
+    if (rem) *rem = split ? r : 0;
+    return split ? 1 : 0;
+}
+
+// (nfull, rem) of the last launch of the non-persistent NT kernel by this process, (T, 0) when it was not split, (-1, -1) before
+// the first one or after a reset: host-side bookkeeping for tests (which kernel a shape reached, and whether its tail was split)
+static int sc_last_tail[2] = {-1, -1};
+extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset) {
+    if (nfull) *nfull = sc_last_tail[0];
+    if (rem) *rem = sc_last_tail[1];
+    if (reset) sc_last_tail[0] = sc_last_tail[1] = -1;
+    return 0;
+}
+
+// workgroup slots of the current device = its CU count (queried once per device)
+static int sc_gemm_slots() {
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cus[dev] == 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = -1;
+        cus[dev] = n;
+    }
+    return cus[dev] > 0 ? cus[dev] : 0;
+}
+
+// Which launch classes take the tail split by default.  Measured per class on the step's shapes (M = 50 432, alone on the chip,
+// switch off -> on, profiles/gemm_tail_summary.txt): N = 768 (591 tiles, 2.31 rounds) plain K = 768 / 2304 / 3072 67.6 -> 61.2 /
+// 165.2 -> 153.4 / 213.7 -> 199.4 us, bf16 residual K = 768 / 3072 82.6 -> 72.0 / 237.2 -> 215.2, fp32 residual K = 768 117.2 ->
+// 108.8; N = 3072 (2 364 tiles, 9.23 rounds) act-pair 303.1 -> 295.9, x act' 278.8 -> 274.6.  Every class gains, the short-K ones
+// (where a half tile's fixed prologue and epilogue weigh most) the most in relative terms: none is excluded.
+static bool sc_tail_default(int epi, const GemmArgs& g) {
+    (void)epi; (void)g;
+    return true;
+}
+
 int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, hipStream_t st) {
     if (g.M < 256 || g.N < 192 || (g.K % BK) != 0) return 0;
     if (mode == SC_GEMM_TN && (epi != SC_EPI_F32 || (g.M % 8) != 0 || (g.N % 8) != 0)) return 0;
@@ -1470,9 +1723,25 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
             g.band_rows = (g.ntm + 7) / 8;                       // an XCD's contiguous share of the remapped tile list
         }
     }
+    // Tail split: SC_GEMM_TAIL (A/B switch, read per call) unset = the rule with the device's CU count for the classes of
+    // sc_tail_default, 0 = off, <n> = the rule with S = n for every class (the result does not depend on S).
+    g.tail_first = g.tail_rem = 0;
+    int grid = nblocks;
+    if (splitk == 1) {
+        const char* sw = getenv("SC_GEMM_TAIL");
+        const int slots = sw ? atoi(sw) : (sc_tail_default(epi, g) ? sc_gemm_slots() : 0);
+        int nfull = 0, rem = 0;
+        if (slots > 0 && sc_debug_gemm_tail_rule(nblocks, slots, &nfull, &rem)) {
+            g.tail_first = nfull;
+            g.tail_rem = rem;
+            grid = nfull + 2 * rem;
+        }
+    }
+    sc_last_tail[0] = g.tail_first > 0 ? g.tail_first : nblocks;
+    sc_last_tail[1] = g.tail_rem;
     int rc = 0;
 #define SC_CASE(EPI) \
-    if (epi == EPI) rc = launch<EPI>(g, nblocks, st);
+    if (epi == EPI) rc = launch<EPI>(g, grid, st);
     SC_CASE(SC_EPI_BF16)
     SC_CASE(SC_EPI_BF16_BIAS)
     SC_CASE(SC_EPI_F32_BIAS_RES)

@@ -52,6 +52,11 @@ struct GemmArgs {
     // group by column group (Gc column tiles: a B sub-panel that stays in the XCD's 4-MB L2 while the band's rows stream by)
     int col_group = 0;
     int band_rows = 0;
+    // tail split of gemm8p_kernel (sc_gemm8p_try): 0 = every workgroup computes a 256x256 tile; nfull > 0 = workgroups
+    // [0, nfull) compute the first nfull tiles of the walk, the 2 * tail_rem workgroups after them the remaining tail_rem
+    // tiles as 128-row half tiles (the partial last round of tiles, spread over twice as many CUs)
+    int tail_first = 0;
+    int tail_rem = 0;
 };
 
 // (tm, tn) of remapped tile index idx under the column-group walk (splitk == 1)

@@ -17,3 +17,9 @@ enum sc_attn_path {
 // take under the current environment switches; -1 with sc_attn_fwd's own message for a shape they refuse.  No HIP call.
 extern "C" int sc_debug_attn_last_path(int* fwd, int* bwd);
 extern "C" int sc_debug_attn_plan(int B, int L, int H, int dh, int causal, int q_rows, int* fwd, int* bwd);
+// sc_debug_gemm_tail_rule: the tail-split rule of the 256x256 NT kernel for T tiles on S workgroup slots (sc_gemm8p.hip).  Returns 1
+// and (nfull, rem) = (T - T % S, T % S) when the last round is split into 2 rem half tiles, else 0 and (T, 0).  Host arithmetic only.
+extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem);
+// sc_debug_gemm_last_tail: (nfull, rem) of this process's last launch of the non-persistent 256x256 NT kernel ((T, 0): not split;
+// (-1, -1): none since the last reset); reset != 0 clears the record.
+extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset);

@@ -229,6 +229,29 @@ def attn_plan(B: int, L: int, H: int, dh: int, causal: bool = False, q_rows: int
     return ATTN_FWD_PATHS[f.value], ATTN_BWD_PATHS[b.value]
 
 
+def gemm_tail_rule(T: int, S: int):
+    """(nfull, rem) of the NT GEMM's tail split for ``T`` 256x256 tiles on ``S`` workgroup slots: the first ``nfull`` tiles run
+    as full tiles and the last ``rem`` as ``2 * rem`` half tiles; ``(T, 0)`` when the launch is not split
+    (``sc_debug_gemm_tail_rule``: host arithmetic only, so it runs without a GPU)."""
+    fn = getattr(_lib.lib(), "sc_debug_gemm_tail_rule")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.POINTER(ctypes.c_int)] * 2
+    nfull, rem = ctypes.c_int(-1), ctypes.c_int(-1)
+    split = fn(T, S, ctypes.byref(nfull), ctypes.byref(rem))
+    assert bool(split) == (rem.value > 0)
+    return nfull.value, rem.value
+
+
+def gemm_last_tail(reset: bool = False):
+    """(nfull, rem) of the last launch of the non-persistent 256x256 NT kernel by this process: ``(tiles, 0)`` when its tail
+    was not split, ``(-1, -1)`` when there was none since the last ``reset`` (the launch went to another kernel).  A debug
+    hook (``sc_debug_gemm_last_tail``): host-side bookkeeping, no device work."""
+    fn = getattr(_lib.lib(), "sc_debug_gemm_last_tail")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] * 2 + [ctypes.c_int]
+    nfull, rem = ctypes.c_int(-1), ctypes.c_int(-1)
+    fn(ctypes.byref(nfull), ctypes.byref(rem), int(reset))
+    return nfull.value, rem.value
+
+
 # ------------------------------------------------------------------------------------------ norms
 def _t8_args(t8, rows: int, d: int, what: str):
     """(buffer uint8 [rows, >= d], scale fp32 [1], amax fp32 [64]) -> ctypes arguments of a per-tensor e4m3 second output."""
