@@ -248,6 +248,32 @@ int sc_embed_ln_bwd(float* dres, const float* patch_out, const float* cls, const
                     const float* rstd, const float* gamma, void* dpatch_bf16, float* dgamma, float* dbeta,
                     float* dpos, float* dcls, float* ws, int B, int L, int d, void* stream);
 
+/* FLIP patch dropout (PatchDropout, src/open_clip/transformer.py:48-89, applied in _embeds at :794): a training forward
+ * keeps K of the n = grid^2 patch tokens of every image plus the class token.
+ * sc_patch_keep: keep[B, K] (int32, ascending per row) and slot[B, n] (kept position of patch j, or -1) of a uniformly random
+ * K-subset per sample.  Key of patch j of sample b = mix32(h ^ j * 0x9E3779B9), h = mix32(mix32(mix32(seed + 0x9E3779B9) ^
+ * draw) ^ (sample0 + b)), mix32 = murmur3's 32-bit finaliser (all arithmetic mod 2^32; the three counters are taken mod 2^32);
+ * kept = the K smallest (key, j).  spatial_clip_amd/patch_dropout.py restates it in numpy, bit for bit.
+ * sc_im2col_keep: the [B*K, ld_out] bf16 patch rows of the kept patches only (inner order c,py,px; K padding untouched).
+ * sc_embed_ln_fwd_keep(_x16): sc_embed_ln_fwd(_x16) at L = K + 1 tokens, token t > 0 of sample b reading patch row
+ * b*K + t - 1 and position keep[b, t-1] + 1; a kept row is bit-identical to the full kernel's row.
+ * sc_embed_ln_bwd_keep: the backward at L = K + 1 (d(token) in place, packed bf16 d(patch out) of B*K rows, dgamma / dbeta;
+ * ws of sc_embed_ln_bwd_ws_floats(B, L, d)); dpos[n + 1, d]: row 0 = dcls = sum_b d(token)[b, 0], row 1 + j = sum over the
+ * samples that kept j in ascending b (through slot), exact zeros where nobody kept j.  No atomics, fixed summation order. */
+int sc_patch_keep(int* keep, int* slot, long long seed, long long draw, long long sample0, int B, int n, int K, void* stream);
+int sc_im2col_keep(const float* images, const int* keep, void* patches, int B, int K, int C, int H, int W, int P,
+                   long long ld_out, void* stream);
+int sc_embed_ln_fwd_keep(const float* patch_out, const float* cls, const float* pos, const int* keep, const float* gamma,
+                         const float* beta, float* x, float* mean, float* rstd, int B, int L, int n, int d, float eps,
+                         void* stream);
+int sc_embed_ln_fwd_keep_x16(const float* patch_out, const float* cls, const float* pos, const int* keep, const float* gamma,
+                             const float* beta, void* x_bf16, float* mean, float* rstd, int B, int L, int n, int d, float eps,
+                             void* stream);
+int sc_embed_ln_bwd_keep(float* dres, const float* patch_out, const float* cls, const float* pos, const int* keep,
+                         const int* slot, const float* mean, const float* rstd, const float* gamma, void* dpatch_bf16,
+                         float* dgamma, float* dbeta, float* dpos, float* dcls, float* ws, int B, int L, int n, int d,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------ text tower glue
  * CLIP.encode_text (src/open_clip/model.py:330-345): x = token_embedding[text] + positional_embedding (fp32 residual
  * stream [B*L, d]); pooling = row at text.argmax(-1) (EOT has the largest id; src/open_clip/transformer.py:931-934).

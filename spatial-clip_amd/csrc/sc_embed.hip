@@ -583,3 +583,390 @@ extern "C" int sc_scatter_rows_f32(const float* src, const int* idx, int L, floa
     SC_LAUNCH_CHECK();
     return 0;
 }
+
+// ============================================================================================ FLIP patch dropout
+// PatchDropout (src/open_clip/transformer.py:48-89), applied after the positional embedding and before ln_pre (:794): a
+// training forward keeps K of the n patch tokens of every image plus the class token.  Here the K kept patches are chosen on
+// the device (sc_patch_keep), kept in ASCENDING patch order (the class-token feature and every gradient are invariant to the
+// token order: the positions are added before the drop), and only those are im2col'd, embedded and normalised; the backward
+// sends d(positional_embedding) back to the kept positions through the inverse map ``slot``.  The kernels of the full-length
+// path above are untouched; the per-row arithmetic below is theirs, expression by expression (a kept row is bit-identical
+// to the full kernel's row).
+namespace {
+
+SC_DEVICE unsigned mix32(unsigned h) {      // murmur3's 32-bit finaliser
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+
+// one workgroup per sample: a key per patch from a counter-based hash (no generator state), rank of patch j = number of
+// patches with a smaller (key, j), kept = rank < K, output position = number of kept patches in front of j
+__global__ __launch_bounds__(256) void patch_keep_kernel(int* __restrict__ keep, int* __restrict__ slot, unsigned seed,
+                                                         unsigned draw, unsigned sample0, int n, int K) {
+    extern __shared__ unsigned pk_smem[];
+    unsigned* key = pk_smem;                 // [n]
+    int* kept = reinterpret_cast<int*>(pk_smem + n);      // [n]
+    const int b = blockIdx.x;
+    unsigned h = mix32(seed + 0x9E3779B9u);
+    h = mix32(h ^ draw);
+    h = mix32(h ^ (sample0 + (unsigned)b));
+    for (int j = threadIdx.x; j < n; j += 256) key[j] = mix32(h ^ ((unsigned)j * 0x9E3779B9u));
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const unsigned kj = key[j];
+        int rank = 0;
+        for (int i = 0; i < n; ++i) {
+            const unsigned ki = key[i];
+            rank += (ki < kj || (ki == kj && i < j)) ? 1 : 0;
+        }
+        kept[j] = rank < K ? 1 : 0;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += 256) {
+        int pos = -1;
+        if (kept[j]) {
+            pos = 0;
+            for (int i = 0; i < j; ++i) pos += kept[i];
+            keep[(long long)b * K + pos] = j;
+        }
+        slot[(long long)b * n + j] = pos;
+    }
+}
+
+SC_DEVICE int keep_at(const int* __restrict__ keep, long long i, int n) {      // a foreign index never leaves the tables
+    const int j = keep[i];
+    return j < 0 ? 0 : (j >= n ? n - 1 : j);
+}
+
+// im2col of the kept patches, generic patch size: one thread per (kept row, c, py) copies P pixels (im2col_kernel's walk)
+__global__ void im2col_keep_kernel(const float* __restrict__ img, const int* __restrict__ keep, bf16* __restrict__ out, int B,
+                                   int K, int C, int H, int W, int P, long long ld_out) {
+    const int G_w = W / P, n = (H / P) * G_w;
+    const long long total = (long long)B * K * C * P;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        long long r = i;
+        const int py = (int)(r % P); r /= P;
+        const int c = (int)(r % C); r /= C;                 // r = kept row b * K + t
+        const int b = (int)(r / K);
+        const int j = keep_at(keep, r, n);
+        const int gy = j / G_w, gx = j - gy * G_w;
+        const float* src = img + (((long long)b * C + c) * H + gy * P + py) * W + gx * P;
+        bf16* dst = out + r * ld_out + (c * P + py) * P;
+        if ((P & 3) == 0 && (W & 3) == 0) {
+            for (int x = 0; x < P; x += 4) {
+                const f32x4 v = ld4(src + x);
+                bf16x4 o;
+                o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
+                *reinterpret_cast<bf16x4*>(dst + x) = o;
+            }
+        } else {
+            for (int x = 0; x < P; ++x) dst[x] = (bf16)src[x];
+        }
+    }
+}
+
+// patch sizes that are multiples of 8: one thread per 16-byte chunk of a kept patch row (8 pixels of one image row: two
+// 16-byte reads), so a wave writes 1 KB of the row contiguously.  The full-length kernel stages whole image strips in LDS; a
+// kept patch owns only P of a strip's W columns, so its 32-byte pieces are read straight from the image.
+__global__ __launch_bounds__(256) void im2col_keep_chunk_kernel(const float* __restrict__ img, const int* __restrict__ keep,
+                                                                bf16* __restrict__ out, int B, int K, int C, int H, int W,
+                                                                int P, long long ld_out) {
+    const int G_w = W / P, n = (H / P) * G_w;
+    const int p8 = P / 8, cpr = C * P * p8;                  // 16-byte chunks per patch row
+    const long long total = (long long)B * K * cpr;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / cpr;
+        const int q = (int)(i - r * cpr);
+        const int row = q / p8, px0 = (q - row * p8) * 8;   // row = c * P + py
+        const int c = row / P, py = row - c * P;
+        const int b = (int)(r / K);
+        const int j = keep_at(keep, r, n);
+        const int gy = j / G_w, gx = j - gy * G_w;
+        const float* src = img + (((long long)b * C + c) * H + gy * P + py) * W + gx * P + px0;
+        const f32x4 v0 = ld4(src), v1 = ld4(src + 4);
+        bf16x8 o;
+        o[0] = (bf16)v0[0]; o[1] = (bf16)v0[1]; o[2] = (bf16)v0[2]; o[3] = (bf16)v0[3];
+        o[4] = (bf16)v1[0]; o[5] = (bf16)v1[1]; o[6] = (bf16)v1[2]; o[7] = (bf16)v1[3];
+        *reinterpret_cast<bf16x8*>(out + r * ld_out + (long long)q * 8) = o;
+    }
+}
+
+// embed_ln_fwd_kernel with the position row looked up: token t > 0 of sample b reads patch row b * K + t - 1 (K = L - 1, as in
+// the full kernel with L tokens) and position keep[b, t - 1] + 1
+template <int NV, bool XB = false>
+__global__ __launch_bounds__(256) void embed_ln_fwd_keep_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
+                                                                const float* __restrict__ pos, const int* __restrict__ keep,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float* __restrict__ x, float* __restrict__ mean,
+                                                                float* __restrict__ rstd, int B, int L, int n, int d, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (row >= B * L) return;
+    const int b = row / L, tkn = row - b * L;
+    const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
+    const int ptk = tkn == 0 ? 0 : keep_at(keep, (long long)b * (L - 1) + (tkn - 1), n) + 1;
+    const float* pr = pos + (long long)ptk * d;
+    const int nv = d >> 2;
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = i * 64 + lane;
+        if (e < nv) {
+            v[i] = ld4(src + e * 4) + ld4(pr + e * 4);
+            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
+        }
+    }
+    const float mu = sc_wave_sum(s) / (float)d;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = i * 64 + lane;
+        if (e < nv) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { const float u = v[i][c] - mu; q += u * u; }
+        }
+    }
+    const float rs = rsqrtf(sc_wave_sum(q) / (float)d + eps);
+    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = i * 64 + lane;
+        if (e < nv) {
+            const f32x4 g = ld4(gamma + e * 4), bb = ld4(beta + e * 4);
+            f32x4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = (v[i][c] - mu) * rs * g[c] + bb[c];
+            if (XB) {
+                bf16x4 ob;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) ob[c] = (bf16)o[c];
+                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(x) + (long long)row * d + e * 4) = ob;
+            } else {
+                st4(x + (long long)row * d + e * 4, o);
+            }
+        }
+    }
+}
+
+// embed_ln_bwd_kernel with the position row looked up (same row loop, same partial sums of dgamma / dbeta)
+template <int NV>
+__global__ __launch_bounds__(256) void embed_ln_bwd_keep_kernel(float* __restrict__ dres, const float* __restrict__ patch,
+                                                                const float* __restrict__ cls, const float* __restrict__ pos,
+                                                                const int* __restrict__ keep, const float* __restrict__ mean,
+                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                                bf16* __restrict__ dpatch, float* __restrict__ partial, int B,
+                                                                int L, int n, int d) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nv = d >> 2;
+    const int rows = B * L;
+    f32x4 ag[NV], ab[NV], gm[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        ag[i] = ab[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        const int e = i * 64 + lane;
+        gm[i] = e < nv ? ld4(gamma + e * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+        const int b = row / L, tkn = row - b * L;
+        const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
+        const int ptk = tkn == 0 ? 0 : keep_at(keep, (long long)b * (L - 1) + (tkn - 1), n) + 1;
+        const float* pr = pos + (long long)ptk * d;
+        const float mu = mean[row], rs = rstd[row];
+        float* dr = dres + (long long)row * d;
+        f32x4 g[NV], xh[NV];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = i * 64 + lane;
+            if (e < nv) {
+                const f32x4 dyv = ld4(dr + e * 4);
+                const f32x4 xv = ld4(src + e * 4) + ld4(pr + e * 4);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    xh[i][c] = (xv[c] - mu) * rs;
+                    g[i][c] = dyv[c] * gm[i][c];
+                    s1 += g[i][c];
+                    s2 += g[i][c] * xh[i][c];
+                    ag[i][c] += dyv[c] * xh[i][c];
+                    ab[i][c] += dyv[c];
+                }
+            }
+        }
+        s1 = sc_wave_sum(s1) / (float)d;
+        s2 = sc_wave_sum(s2) / (float)d;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = i * 64 + lane;
+            if (e < nv) {
+                f32x4 o;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) o[c] = rs * (g[i][c] - s1 - xh[i][c] * s2);
+                st4(dr + e * 4, o);
+                if (tkn > 0) {
+                    bf16x4 ob;
+                    ob[0] = (bf16)o[0]; ob[1] = (bf16)o[1]; ob[2] = (bf16)o[2]; ob[3] = (bf16)o[3];
+                    *reinterpret_cast<bf16x4*>(dpatch + ((long long)b * (L - 1) + (tkn - 1)) * d + e * 4) = ob;
+                }
+            }
+        }
+    }
+    float* sm = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int e = i * 64 + lane;
+        if (e < nv) {
+            st4(sm + (wave * 2 + 0) * d + e * 4, ag[i]);
+            st4(sm + (wave * 2 + 1) * d + e * 4, ab[i]);
+        }
+    }
+    __syncthreads();
+    float* pout = partial + (long long)blockIdx.x * 2 * d;
+    for (int e = threadIdx.x; e < 2 * d; e += 256) pout[e] = sm[e] + sm[2 * d + e] + sm[4 * d + e] + sm[6 * d + e];
+}
+
+// d(positional_embedding) of a dropping pass, one workgroup per position row p (all n + 1 rows are written): row 0 sums the class
+// tokens of every sample (and is d(class_embedding) too), row 1 + j sums d(token) of the samples that kept patch j, found
+// through slot[b, j] (block-uniform: scalar loads).  One accumulator per element, samples in ascending order, four rows in
+// flight; a sample that dropped j adds +0.0, so a patch nobody kept gets exact zeros.  No atomics: bit-reproducible.
+__global__ __launch_bounds__(256) void dpos_keep_kernel(const float* __restrict__ dres, const int* __restrict__ slot,
+                                                        float* __restrict__ dpos, float* __restrict__ dcls, int B, int L, int n,
+                                                        int d) {
+    const int p = blockIdx.x;
+    const int nv = d >> 2;
+    for (int e = threadIdx.x; e < nv; e += 256) {
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int b0 = 0; b0 < B; b0 += 4) {
+            f32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int b = b0 + u;
+                v[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (b < B) {
+                    const int s = p == 0 ? 0 : slot[(long long)b * n + (p - 1)] + 1;      // token row inside the sample, 0 = dropped
+                    if (p == 0 || (s > 0 && s < L)) v[u] = ld4(dres + ((long long)b * L + s) * d + e * 4);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc += v[u];
+        }
+        st4(dpos + (long long)p * d + e * 4, acc);
+        if (p == 0) st4(dcls + e * 4, acc);
+    }
+}
+
+}  // namespace
+
+extern "C" int sc_patch_keep(int* keep, int* slot, long long seed, long long draw, long long sample0, int B, int n, int K,
+                             void* stream) {
+    SC_CHECK(B > 0 && n > 0 && n <= 4096 && K > 0 && K <= n && keep != nullptr && slot != nullptr,
+             "sc_patch_keep: bad shape B=%d n=%d K=%d", B, n, K);
+    patch_keep_kernel<<<B, 256, (size_t)n * 8, (hipStream_t)stream>>>(keep, slot, (unsigned)(seed & 0xffffffffll),
+                                                                      (unsigned)(draw & 0xffffffffll),
+                                                                      (unsigned)(sample0 & 0xffffffffll), n, K);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_im2col_keep(const float* images, const int* keep, void* patches, int B, int K, int C, int H, int W, int P,
+                              long long ld_out, void* stream) {
+    SC_CHECK(B > 0 && C > 0 && P > 0 && H % P == 0 && W % P == 0, "sc_im2col_keep: bad shape B=%d C=%d H=%d W=%d P=%d", B, C,
+             H, W, P);
+    SC_CHECK(K > 0 && K <= (H / P) * (W / P) && keep != nullptr, "sc_im2col_keep: bad K=%d", K);
+    SC_CHECK(ld_out >= (long long)C * P * P && (ld_out % 4) == 0, "sc_im2col_keep: ld_out too small / unaligned");
+    if ((P % 8) == 0 && (W % 8) == 0 && (ld_out % 8) == 0) {
+        const long long total = (long long)B * K * C * P * (P / 8);
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 16384) blocks = 16384;
+        im2col_keep_chunk_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(images, keep, (bf16*)patches, B, K, C, H, W, P, ld_out);
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
+    const long long total = (long long)B * K * C * P;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    im2col_keep_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(images, keep, (bf16*)patches, B, K, C, H, W, P, ld_out);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+static int embed_ln_fwd_keep_launch(const float* patch_out, const float* cls, const float* pos, const int* keep,
+                                    const float* gamma, const float* beta, float* x, bool xb, float* mean, float* rstd, int B,
+                                    int L, int n, int d, float eps, void* stream) {
+#define SC_EMBED_FWD_KEEP(NV)                                                                                                      \
+    do {                                                                                                                          \
+        if (xb) embed_ln_fwd_keep_kernel<NV, true><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(                             \
+            patch_out, cls, pos, keep, gamma, beta, x, mean, rstd, B, L, n, d, eps);                                              \
+        else embed_ln_fwd_keep_kernel<NV, false><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(                               \
+            patch_out, cls, pos, keep, gamma, beta, x, mean, rstd, B, L, n, d, eps);                                              \
+    } while (0)
+    switch ((d / 4 + 63) / 64) {
+        case 1: SC_EMBED_FWD_KEEP(1); break;
+        case 2: SC_EMBED_FWD_KEEP(2); break;
+        case 3: SC_EMBED_FWD_KEEP(3); break;
+        case 4: SC_EMBED_FWD_KEEP(4); break;
+        case 5: SC_EMBED_FWD_KEEP(5); break;
+        case 6: SC_EMBED_FWD_KEEP(6); break;
+        case 7: SC_EMBED_FWD_KEEP(7); break;
+        default: SC_EMBED_FWD_KEEP(8); break;
+    }
+#undef SC_EMBED_FWD_KEEP
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_embed_ln_fwd_keep(const float* patch_out, const float* cls, const float* pos, const int* keep,
+                                    const float* gamma, const float* beta, float* x, float* mean, float* rstd, int B, int L,
+                                    int n, int d, float eps, void* stream) {
+    SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr,
+             "sc_embed_ln_fwd_keep: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
+    return embed_ln_fwd_keep_launch(patch_out, cls, pos, keep, gamma, beta, x, false, mean, rstd, B, L, n, d, eps, stream);
+}
+
+extern "C" int sc_embed_ln_fwd_keep_x16(const float* patch_out, const float* cls, const float* pos, const int* keep,
+                                        const float* gamma, const float* beta, void* x_bf16, float* mean, float* rstd, int B,
+                                        int L, int n, int d, float eps, void* stream) {
+    SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr && x_bf16 != nullptr,
+             "sc_embed_ln_fwd_keep_x16: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
+    return embed_ln_fwd_keep_launch(patch_out, cls, pos, keep, gamma, beta, (float*)x_bf16, true, mean, rstd, B, L, n, d, eps,
+                                    stream);
+}
+
+extern "C" int sc_embed_ln_bwd_keep(float* dres, const float* patch_out, const float* cls, const float* pos, const int* keep,
+                                    const int* slot, const float* mean, const float* rstd, const float* gamma,
+                                    void* dpatch_bf16, float* dgamma, float* dbeta, float* dpos, float* dcls, float* ws, int B,
+                                    int L, int n, int d, void* stream) {
+    SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr && slot != nullptr,
+             "sc_embed_ln_bwd_keep: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
+    hipStream_t st = (hipStream_t)stream;
+    int nblk = (B * L + 3) / 4;
+    if (nblk > 1024) nblk = 1024;      // the workspace of sc_embed_ln_bwd_ws_floats(B, L, d)
+    const size_t lds = (size_t)4 * 2 * d * sizeof(float);
+#define SC_EMBED_BWD_KEEP(NV)                                                                                         \
+    do {                                                                                                              \
+        if (lds > 48 * 1024)                                                                                          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_ln_bwd_keep_kernel<NV>),                   \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
+        embed_ln_bwd_keep_kernel<NV><<<nblk, 256, lds, st>>>(dres, patch_out, cls, pos, keep, mean, rstd, gamma,      \
+                                                             (bf16*)dpatch_bf16, ws, B, L, n, d);                     \
+    } while (0)
+    switch ((d / 4 + 63) / 64) {
+        case 1: SC_EMBED_BWD_KEEP(1); break;
+        case 2: SC_EMBED_BWD_KEEP(2); break;
+        case 3: SC_EMBED_BWD_KEEP(3); break;
+        case 4: SC_EMBED_BWD_KEEP(4); break;
+        case 5: SC_EMBED_BWD_KEEP(5); break;
+        case 6: SC_EMBED_BWD_KEEP(6); break;
+        case 7: SC_EMBED_BWD_KEEP(7); break;
+        default: SC_EMBED_BWD_KEEP(8); break;
+    }
+#undef SC_EMBED_BWD_KEEP
+    SC_LAUNCH_CHECK();
+    colvec2_finalize_kernel<<<(2 * d + 63) / 64, 1024, 0, st>>>(ws, nblk, d, dgamma, dbeta);
+    SC_LAUNCH_CHECK();
+    dpos_keep_kernel<<<n + 1, 256, 0, st>>>(dres, slot, dpos, dcls, B, L, n, d);
+    SC_LAUNCH_CHECK();
+    return 0;
+}

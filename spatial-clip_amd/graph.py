@@ -77,6 +77,8 @@ class GraphedTrainStep:
             return "multi-rank step (RCCL collectives stay eager)"
         if getattr(net, "precision", "bf16") != "bf16":
             return "e4m3 path (amax-history slot is a host-side counter)"
+        if getattr(net, "patch_dropout", 0.0) > 0.0:
+            return "patch dropout (the draw counter of the kept patches is a host-side argument)"
         if getattr(self.opt, "exchange", None) is not None:
             return "sharded optimiser"
         if os.environ.get("SC_OVERLAP", "auto") not in ("0", "1"):

@@ -18,6 +18,8 @@ class VisionCfg:
     layers: int = 12
     head_width: int = 64
     mlp_ratio: float = 4.0
+    # FLIP patch dropout (open_clip vision_cfg.patch_dropout): fraction of the patch tokens a TRAINING forward drops, 0 = off
+    patch_dropout: float = 0.0
 
     @property
     def heads(self) -> int:

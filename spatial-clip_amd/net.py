@@ -18,9 +18,10 @@ from typing import Any, Callable, Dict, List, Optional
 
 import torch
 
-from . import ops, streams
+from . import comm, ops, streams
 from .model_configs import ModelCfg, check_attention_support, get_model_config, with_image_size
 from .params import ParamStore
+from .patch_dropout import check_fraction
 from .towers import GeneTower, GeneTransformerTower, TextTower, VisionTower
 
 OPENAI_DATASET_MEAN = (0.48145466, 0.4578275, 0.40821073)   # src/open_clip/constants.py:1-2
@@ -218,8 +219,11 @@ class SpatialClipNet(torch.nn.Module):
                  device: Optional[str] = None, seed: int = 0, model_cfg: Optional[ModelCfg] = None,
                  tokenizer_vocab: Optional[str] = None, precision: str = "bf16", grad_checkpointing: bool = False,
                  residual_stream: str = "bf16", init_logit_scale: Optional[float] = None,
-                 init_logit_bias: Optional[float] = None, force_image_size: Optional[int] = None):
+                 init_logit_bias: Optional[float] = None, force_image_size: Optional[int] = None,
+                 force_patch_dropout: Optional[float] = None):
         super().__init__()
+        if force_patch_dropout is not None:
+            check_fraction(force_patch_dropout)     # ValueError outside [0, 1), before anything is built
         if aug_cfg is not None and not isinstance(aug_cfg, (dict, AugmentationCfg)) and not is_dataclass(aug_cfg) \
                 and not hasattr(aug_cfg, "items"):
             raise TypeError(f"Unsupported type for aug_cfg: {type(aug_cfg)}")     # spatial_clip_net.py:33-34
@@ -236,6 +240,11 @@ class SpatialClipNet(torch.nn.Module):
             # open_clip's create_model(force_image_size=...) (src/open_clip/factory.py:438-439): the vision tower's input
             # size, and with it the token count; a checkpoint's positions are resized to it on load
             self.cfg = with_image_size(self.cfg, force_image_size)
+        if force_patch_dropout is not None and self.cfg.vision is not None:
+            # open_clip's create_model(force_patch_dropout=...) (src/open_clip/factory.py:436-437) overrides vision_cfg.patch_dropout
+            self.cfg = replace(self.cfg, vision=replace(self.cfg.vision, patch_dropout=check_fraction(force_patch_dropout)))
+        if self.cfg.vision is not None:
+            check_fraction(self.cfg.vision.patch_dropout)       # [0, 1), like the reference's PatchDropout (transformer.py:56)
         if self.cfg.gene is None and self.cfg.text is None:
             raise ValueError(f"{model_name}: the model config has neither a text tower nor a gene tower")
         check_attention_support(self.cfg)       # e.g. ViT-H-14 at 378 px: head dim 80 has no kernel above 320 tokens
@@ -249,6 +258,13 @@ class SpatialClipNet(torch.nn.Module):
             p._sc_store = self.store
             self.register_parameter(name.replace(".", "__"), p)
         self.vision = VisionTower(self.cfg, self.store)
+        # FLIP patch dropout: the subset a training forward keeps is a function of (seed, draw, rank, sample, patch);
+        # ``patch_dropout_draw`` counts the dropping forwards of this net.  Host state, not a parameter and not in state_dict (the
+        # checkpoint layout is the reference's): Trainer.save_checkpoint / load_checkpoint carry it beside the weights.
+        self.seed = int(seed)
+        self.patch_dropout = self.vision.patch_dropout
+        self.patch_dropout_draw = 0
+        self._patch_keep_next = None
         if self.cfg.gene is not None:
             gene_cls = GeneTransformerTower if self.cfg.gene.kind == "transformer" else GeneTower
             self.second = gene_cls(self.cfg, self.store)
@@ -437,7 +453,14 @@ class SpatialClipNet(torch.nn.Module):
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, images: torch.Tensor, texts: torch.Tensor) -> Dict[str, torch.Tensor]:
-        self._mark_pass(torch.is_grad_enabled())    # read HERE: inside autograd.Function.forward grad mode is always off
+        train_pass = torch.is_grad_enabled()        # read HERE: inside autograd.Function.forward grad mode is always off
+        self._mark_pass(train_pass)
+        if self.patch_dropout > 0.0 and train_pass and self.training:
+            # this forward drops patches: arm the vision tower for it (the class token and a fresh K-subset per sample)
+            self.vision.drop = {"seed": self.seed, "draw": self.patch_dropout_draw, "rank": comm.world()[0],
+                                "keep": self._patch_keep_next}
+            self._patch_keep_next = None
+            self.patch_dropout_draw += 1
         out = _NetFn.apply(self.store.params["logit_scale"], self, images, texts)
         img, txt, s = out[:3]
         return {"image_features": img, "text_features": txt, "logit_scale": s,
@@ -450,6 +473,22 @@ class SpatialClipNet(torch.nn.Module):
         that, so they give the numbers a fresh process gives for the same weights (advisor, rounds 3-4)."""
         for _, stack in self._stacks():
             stack.fp8_train_pass = bool(train_pass)
+        self.vision.drop = None         # patch dropout is armed by forward() alone, for a training forward
+
+    def set_patch_keep(self, idx) -> None:
+        """Test hook: the NEXT training forward keeps exactly the patches ``idx`` (integer [B, K], K = num_keep(n, p), strictly
+        ascending per row, values in [0, n)) instead of drawing them; ``None`` withdraws it.  Consumed by that one forward."""
+        if idx is None:
+            self._patch_keep_next = None
+            return
+        if self.patch_dropout <= 0.0:
+            raise ValueError("set_patch_keep: this net was built without patch dropout")
+        from .patch_dropout import num_keep, validate_keep
+        n = self.cfg.vision.tokens - 1
+        a = torch.as_tensor(idx)
+        if a.dim() != 2:
+            raise ValueError(f"patch keep indices must be [B, K], got {tuple(a.shape)}")
+        self._patch_keep_next = torch.from_numpy(validate_keep(a, a.shape[0], n, num_keep(n, self.patch_dropout)))
 
     def _bucket(self, names: List[str]) -> None:
         if self.grad_bucket_hook is not None:

@@ -430,33 +430,86 @@ def cast_transpose_bf16(src, dst, rows: int, cols: int, ld_dst=None):
 
 
 # ------------------------------------------------------------------------------------------ patch embedding
-def im2col(images, patches, P: int, ld_out: Optional[int] = None):
+def _req_keep(keep, B: int, K: int, name: str = "keep") -> None:
+    _req(keep, torch.int32, name)
+    if tuple(keep.shape) != (B, K) or not keep.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 [{B}, {K}] tensor, got {tuple(keep.shape)}")
+
+
+def patch_keep(seed: int, draw: int, sample0: int, B: int, n: int, K: int, keep=None, slot=None, device=None):
+    """FLIP patch dropout: (keep int32 [B, K] ascending, slot int32 [B, n]) of draw ``draw`` for samples sample0 .. sample0 + B - 1
+    (sc_patch_keep; patch_dropout.keep_indices_host gives the same bits on the host)."""
+    if keep is None:
+        keep = torch.empty((B, K), dtype=torch.int32, device=device or "cuda")
+    if slot is None:
+        slot = torch.empty((B, n), dtype=torch.int32, device=keep.device)
+    _req_keep(keep, B, K)
+    _req_keep(slot, B, n, "slot")
+    check(_lib.lib().sc_patch_keep(keep.data_ptr(), slot.data_ptr(), int(seed), int(draw), int(sample0), B, n, K, _stream()),
+          "sc_patch_keep")
+    return keep, slot
+
+
+def im2col(images, patches, P: int, ld_out: Optional[int] = None, keep=None):
+    """``keep`` (int32 [B, K], FLIP patch dropout): only the kept patches' rows, [B*K, ld_out] (sc_im2col_keep)."""
     _req(images, torch.float32, "images"); _req(patches, torch.bfloat16, "patches")
     B, C, H, W = images.shape
     if not images.is_contiguous():
         raise ValueError("images must be contiguous NCHW")
+    if keep is not None:
+        K = keep.shape[1]
+        _req_keep(keep, B, K)
+        if patches.shape[0] < B * K:
+            raise ValueError(f"patches: {B * K} rows needed, got {patches.shape[0]}")
+        check(_lib.lib().sc_im2col_keep(images.data_ptr(), keep.data_ptr(), patches.data_ptr(), B, K, C, H, W, P,
+                                        ld_out or patches.stride(0), _stream()), "sc_im2col_keep")
+        return patches
     check(_lib.lib().sc_im2col(images.data_ptr(), patches.data_ptr(), B, C, H, W, P, ld_out or patches.stride(0),
                                _stream()), "sc_im2col")
     return patches
 
 
-def embed_ln_fwd(patch_out, cls, pos, gamma, beta, x, mean, rstd, B: int, L: int, d: int, eps: float = 1e-5):
+def embed_ln_fwd(patch_out, cls, pos, gamma, beta, x, mean, rstd, B: int, L: int, d: int, eps: float = 1e-5, keep=None):
     """class token + positional embedding + ln_pre -> the residual stream ``x`` [B*L, d]: fp32, or bf16 (sc_embed_ln_fwd_x16)
-    when the stream is kept in bf16."""
-    if x.dtype == torch.bfloat16:
-        _req(x, torch.bfloat16, "x")
+    when the stream is kept in bf16.  ``keep`` (int32 [B, L - 1], FLIP patch dropout): ``patch_out`` holds the kept patches'
+    rows only and token t > 0 takes position keep[b, t - 1] + 1 of ``pos`` (sc_embed_ln_fwd_keep / _keep_x16)."""
+    x16 = x.dtype == torch.bfloat16
+    _req(x, torch.bfloat16 if x16 else torch.float32, "x")
+    if keep is not None:
+        _req_keep(keep, B, L - 1)
+        what = "sc_embed_ln_fwd_keep_x16" if x16 else "sc_embed_ln_fwd_keep"
+        check(getattr(_lib.lib(), what)(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(), gamma.data_ptr(),
+                                        beta.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, L,
+                                        pos.shape[0] - 1, d, float(eps), _stream()), what)
+        return x
+    if x16:
         fn, what = _lib.lib().sc_embed_ln_fwd_x16, "sc_embed_ln_fwd_x16"
     else:
-        _req(x, torch.float32, "x")
         fn, what = _lib.lib().sc_embed_ln_fwd, "sc_embed_ln_fwd"
     check(fn(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr(), x.data_ptr(),
              mean.data_ptr(), rstd.data_ptr(), B, L, d, float(eps), _stream()), what)
     return x
 
 
-def embed_ln_bwd(dres, patch_out, cls, pos, mean, rstd, gamma, dpatch_bf16, dgamma, dbeta, dpos, dcls, B, L, d):
+def embed_ln_bwd(dres, patch_out, cls, pos, mean, rstd, gamma, dpatch_bf16, dgamma, dbeta, dpos, dcls, B, L, d, keep=None,
+                 slot=None):
+    """``keep`` / ``slot`` (int32 [B, L - 1] / [B, n], FLIP patch dropout): the backward of the dropping forward at L = K + 1
+    tokens; ``dpos`` has all n + 1 rows, exact zeros where no sample kept the patch (sc_embed_ln_bwd_keep)."""
     l = _lib.lib()
     ws = workspace(l.sc_embed_ln_bwd_ws_floats(B, L, d), dres.device, "embed")
+    if keep is not None:
+        n = pos.shape[0] - 1
+        _req_keep(keep, B, L - 1)
+        if slot is None:
+            raise ValueError("embed_ln_bwd(keep=...) needs the inverse map slot [B, n] as well")
+        _req_keep(slot, B, n, "slot")
+        if dpos.numel() != (n + 1) * d:
+            raise ValueError(f"dpos: expected {(n + 1) * d} elements, got {dpos.numel()}")
+        check(l.sc_embed_ln_bwd_keep(dres.data_ptr(), patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(),
+                                     slot.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                     dpatch_bf16.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), dpos.data_ptr(),
+                                     dcls.data_ptr(), ws.data_ptr(), B, L, n, d, _stream()), "sc_embed_ln_bwd_keep")
+        return
     check(l.sc_embed_ln_bwd(dres.data_ptr(), patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), mean.data_ptr(),
                             rstd.data_ptr(), gamma.data_ptr(), dpatch_bf16.data_ptr(), dgamma.data_ptr(),
                             dbeta.data_ptr(), dpos.data_ptr(), dcls.data_ptr(), ws.data_ptr(), B, L, d, _stream()),

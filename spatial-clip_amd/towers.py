@@ -71,13 +71,19 @@ def _group_ok(mode: str, branch: str, shapes, k: int) -> bool:
 
 
 class _Bufs:
-    """Named device buffers, (re)allocated when the requested shape changes."""
+    """Named device buffers, (re)allocated when the requested shape changes.  ``suffix`` is appended to every name asked for
+    while it is set: a pass of another token count (the FLIP patch-dropout training forward / backward beside full-length
+    evaluation) gets buffers of its own instead of reallocating the other pass's at every switch; ``shared=True`` opts a
+    buffer out (its shape does not depend on the token count)."""
 
     def __init__(self, device):
         self.device = device
+        self.suffix = ""
         self._b: Dict[str, torch.Tensor] = {}
 
-    def get(self, name: str, shape, dtype) -> torch.Tensor:
+    def get(self, name: str, shape, dtype, shared: bool = False) -> torch.Tensor:
+        if self.suffix and not shared:
+            name = name + self.suffix
         t = self._b.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
             t = torch.empty(shape, dtype=dtype, device=self.device)
@@ -191,7 +197,7 @@ class TransformerStack:
         return ops.gemm_fp8(epi, q8[0], q8[1], cp.w8, cp.w8s, out, M=M, N=N, K=K, **kw)
 
     def _zero_bias(self, n: int) -> torch.Tensor:
-        z = self.bufs.get("zero.bias", (n,), F32)
+        z = self.bufs.get("zero.bias", (n,), F32, shared=True)
         if not getattr(self, "_zero_bias_set", False):
             z.zero_()
             self._zero_bias_set = True
@@ -737,10 +743,16 @@ class PatchTransformerTower:
         raise NotImplementedError
 
     def forward(self, inp: torch.Tensor) -> torch.Tensor:
-        s, d, D, L = self.s, self.d, self.D, self.L
+        s, d, D = self.s, self.d, self.D
         s.wait_names(self.param_names_stem())
+        self._keep = None             # (keep [B, K], slot [B, n]) of a dropping pass: set by _patchify (VisionTower)
+        self.bufs.suffix = self.stack.bufs.suffix = ""
         patches = self._patchify(inp)
         B = self.B
+        keep = self._keep[0] if self._keep is not None else None
+        # effective token count of THIS pass: K + 1 when patches are dropped; its activations live under their own buffer names
+        L = self.L_run = self.L if keep is None else keep.shape[1] + 1
+        self.bufs.suffix = self.stack.bufs.suffix = "" if keep is None else ".keep"
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
         patch_out = bf.get("patch_out", (Mp, d), F32)
@@ -751,7 +763,7 @@ class PatchTransformerTower:
         x0 = bf.get("x0.16", (M, d), BF16) if r16 else bf.get("x0", (M, d), F32)
         ops.embed_ln_fwd(patch_out, s.p(self._n("class_embedding")), s.p(self._n("positional_embedding")),
                          s.p(self._n("ln_pre.weight")), s.p(self._n("ln_pre.bias")), x0,
-                         bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32), B, L, d)
+                         bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32), B, L, d, keep=keep)
         xf = self.stack.forward(x0, B, L)
         self.xf = xf
         s.wait_names(self.param_names_head())
@@ -771,7 +783,11 @@ class PatchTransformerTower:
         return self.bufs.get("f_raw", (self.B, self.D), F32)
 
     def backward(self, d_f: torch.Tensor, on_bucket: Optional[Callable[[List[str]], None]] = None) -> None:
-        s, d, D, L, B = self.s, self.d, self.D, self.L, self.B
+        s, d, D, B = self.s, self.d, self.D, self.B
+        # the token count and the buffers of the forward this backward belongs to (K + 1 tokens after a dropping forward)
+        L = getattr(self, "L_run", self.L)
+        keep, slot = self._keep if getattr(self, "_keep", None) is not None else (None, None)
+        self.bufs.suffix = self.stack.bufs.suffix = "" if keep is None else ".keep"
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
         d_raw = bf.get("d_raw", (B, D), BF16)
@@ -807,7 +823,7 @@ class PatchTransformerTower:
         ops.embed_ln_bwd(dres, bf.get("patch_out", (Mp, d), F32), s.p(self._n("class_embedding")),
                          s.p(self._n("positional_embedding")), bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32),
                          s.p(self._n("ln_pre.weight")), dpatch, s.g(self._n("ln_pre.weight")), s.g(self._n("ln_pre.bias")),
-                         s.g(self._n("positional_embedding")), s.g(self._n("class_embedding")), B, L, d)
+                         s.g(self._n("positional_embedding")), s.g(self._n("class_embedding")), B, L, d, keep=keep, slot=slot)
         gw = s.g(self._n("conv1.weight")).view(d, self.kp)
         ops.gemm(ops.TN, ops.EPI_F32, dpatch, bf.get("patches", (Mp, self.kp_pad), BF16), gw, M=d, N=self.kp, K=Mp,
                  splitk=_splitk_for(d, self.kp, Mp))
@@ -825,6 +841,31 @@ class VisionTower(PatchTransformerTower):
         self.v = v
         self.quick_gelu = bool(getattr(cfg, "quick_gelu", False))
         super().__init__(cfg, store, v.width, v.heads, v.layers, v.mlp_ratio, v.tokens, 3 * v.patch_size * v.patch_size)
+        # FLIP patch dropout (vision_cfg.patch_dropout; PatchDropout, src/open_clip/transformer.py:48-89): a forward that will be
+        # differentiated, on a net in training mode, keeps K of the n patch tokens.  SpatialClipNet.forward arms ``drop`` for that
+        # one forward -- {"seed", "draw", "rank", "keep" (explicit indices or None)} -- every other forward finds it None and
+        # runs all tokens (validation, the zero-shot bank, encode_image, anything after net.eval()).
+        self.patch_dropout = float(getattr(v, "patch_dropout", 0.0) or 0.0)
+        self.drop: Optional[Dict[str, object]] = None
+        self.keep_idx: Optional[torch.Tensor] = None      # int32 [B, K] of the last dropping forward (ascending patch indices)
+
+    def _select(self, B: int, drop: Dict[str, object]):
+        """(keep [B, K], slot [B, n]) of a dropping forward: drawn on the device (sc_patch_keep), or the explicit indices of
+        SpatialClipNet.set_patch_keep."""
+        from . import patch_dropout as pd
+        n = self.L - 1
+        K = pd.num_keep(n, self.patch_dropout)
+        bf = self.bufs
+        keep, slot = bf.get("keep.idx", (B, K), torch.int32), bf.get("keep.slot", (B, n), torch.int32)
+        given = drop.get("keep")
+        if given is not None:
+            idx = pd.validate_keep(given, B, n, K)
+            keep.copy_(torch.from_numpy(idx))
+            slot.copy_(torch.from_numpy(pd.slots_from_keep(idx, n)))
+        else:
+            ops.patch_keep(drop["seed"], drop["draw"], drop["rank"] * B, B, n, K, keep=keep, slot=slot)
+        self.keep_idx = keep
+        return keep, slot
 
     def _patchify(self, images: torch.Tensor) -> torch.Tensor:
         v = self.v
@@ -832,6 +873,16 @@ class VisionTower(PatchTransformerTower):
             raise ValueError(f"images must be [B,3,{v.image_size},{v.image_size}], got {tuple(images.shape)}")
         images = images.contiguous().float()
         self.B = B = images.shape[0]
+        drop, self.drop = self.drop, None               # armed for ONE forward
+        if drop is not None and self.patch_dropout > 0.0:
+            keep, slot = self._select(B, drop)
+            self._keep = (keep, slot)
+            patches = self.bufs.get("patches.keep", (B * keep.shape[1], self.kp_pad), BF16)
+            if self.kp_pad != self.kp and getattr(self, "_pad_zeroed_keep", None) is not patches:
+                patches.zero_()        # as below: the K padding must be finite zeros
+                self._pad_zeroed_keep = patches
+            ops.im2col(images, patches, v.patch_size, keep=keep)
+            return patches
         patches = self.bufs.get("patches", (B * (self.L - 1), self.kp_pad), BF16)
         if self.kp_pad != self.kp and getattr(self, "_pad_zeroed", None) is not patches:
             patches.zero_()            # the K padding must be finite zeros; im2col only writes the real columns

@@ -314,6 +314,8 @@ class Trainer:
         fp8 = model.net.fp8_scaling_state() if hasattr(model.net, "fp8_scaling_state") else None
         if fp8 is not None:
             ck["fp8_scaling"] = fp8         # delayed e4m3 scales + amax history: a resumed run continues with them
+        if getattr(model.net, "patch_dropout", 0.0) > 0.0:
+            ck["patch_dropout_draw"] = int(model.net.patch_dropout_draw)      # a resumed run draws the subsets the run would have
         torch.save(ck, path)
 
     @staticmethod
@@ -324,6 +326,8 @@ class Trainer:
         model.net.load_checkpoint_state_dict(ck, source=path)          # resets the fp8 scaling history ...
         if hasattr(model.net, "load_fp8_scaling_state"):
             model.net.load_fp8_scaling_state(ck.get("fp8_scaling"))     # ... and restores it when the file carries one
+        if "patch_dropout_draw" in ck and hasattr(model.net, "patch_dropout_draw"):
+            model.net.patch_dropout_draw = int(ck["patch_dropout_draw"])
         if optimizer is not None and isinstance(ck.get("optimizer"), dict) and "exp_avg" in ck["optimizer"]:
             optimizer.load_state_dict({k: (v.to(model.device) if isinstance(v, torch.Tensor) else v)
                                        for k, v in ck["optimizer"].items()})
