@@ -5,14 +5,50 @@
 //   sc_embed_ln_bwd  : LN backward of ln_pre; emits d(token) fp32 (in place), the packed bf16 d(patch out)
 //                      for the conv wgrad GEMM, and dgamma/dbeta
 //   sc_batch_sum     : d(positional_embedding)[t] = sum_b d(token)[b,t]  (row 0 is also d(class_embedding))
+// The *_keep forms of the three are the same passes over the kept patches of a FLIP patch-dropout forward (end of the file).
 #include "sc_common.h"
 #include "sc_kernels.h"
+#include <type_traits>
+#include <utility>
 
 namespace {
 
 constexpr int MAXV = 8;
 SC_DEVICE f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 SC_DEVICE void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+SC_DEVICE bf16x4 bf4(f32x4 v) {
+    bf16x4 o;
+    o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
+    return o;
+}
+SC_DEVICE void stbf4(bf16* p, f32x4 v) { *reinterpret_cast<bf16x4*>(p) = bf4(v); }
+
+SC_DEVICE int keep_at(const int* __restrict__ keep, long long i, int n) {      // a foreign index never leaves the tables
+    const int j = keep[i];
+    return j < 0 ? 0 : (j >= n ? n - 1 : j);
+}
+
+// Row of positional_embedding that token tkn of sample b (L tokens per sample) adds: its own index in a full-length pass; in a
+// patch-dropout pass token tkn > 0 is kept patch keep[b, tkn - 1] of the n patches.  This is ALL that the two passes differ in.
+struct PosFull {
+    SC_DEVICE int operator()(int, int, int tkn) const { return tkn; }
+};
+struct PosKeep {
+    const int* __restrict__ keep;
+    int n;
+    SC_DEVICE int operator()(int b, int L, int tkn) const {
+        return tkn == 0 ? 0 : keep_at(keep, (long long)b * (L - 1) + (tkn - 1), n) + 1;
+    }
+};
+
+// P pixels of one image row -> the (c, py) run of a patch row
+SC_DEVICE void copy_pixel_run(const float* __restrict__ src, bf16* __restrict__ dst, int P, int W) {
+    if ((P & 3) == 0 && (W & 3) == 0) {
+        for (int x = 0; x < P; x += 4) stbf4(dst + x, ld4(src + x));
+    } else {
+        for (int x = 0; x < P; ++x) dst[x] = (bf16)src[x];
+    }
+}
 
 __global__ void im2col_kernel(const float* __restrict__ img, bf16* __restrict__ out, int B, int C, int H, int W, int P,
                               long long ld_out) {
@@ -29,16 +65,7 @@ __global__ void im2col_kernel(const float* __restrict__ img, bf16* __restrict__ 
         const int b = (int)r;
         const float* src = img + (((long long)b * C + c) * H + gy * P + py) * W + gx * P;
         bf16* dst = out + ((long long)(b * G_h + gy) * G_w + gx) * ld_out + (c * P + py) * P;
-        if ((P & 3) == 0 && (W & 3) == 0) {
-            for (int x = 0; x < P; x += 4) {
-                const f32x4 v = ld4(src + x);
-                bf16x4 o;
-                o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
-                *reinterpret_cast<bf16x4*>(dst + x) = o;
-            }
-        } else {
-            for (int x = 0; x < P; ++x) dst[x] = (bf16)src[x];
-        }
+        copy_pixel_run(src, dst, P, W);
     }
 }
 
@@ -56,10 +83,7 @@ __global__ __launch_bounds__(256) void im2col_strip_kernel(const float* __restri
     for (int i = threadIdx.x; i < rows * w4; i += 256) {
         const int row = i / w4, x4 = i - row * w4;
         const int c = row / P, py = row - c * P;
-        const f32x4 v = ld4(img + (((long long)b * C + c) * H + gy * P + py) * W + x4 * 4);
-        bf16x4 o;
-        o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
-        *reinterpret_cast<bf16x4*>(tile + row * W + x4 * 4) = o;
+        stbf4(tile + row * W + x4 * 4, ld4(img + (((long long)b * C + c) * H + gy * P + py) * W + x4 * 4));
     }
     __syncthreads();
     const int cpr = rows * P / 8;                                 // 16-byte chunks per patch row
@@ -74,18 +98,20 @@ __global__ __launch_bounds__(256) void im2col_strip_kernel(const float* __restri
 
 // one wave per token row; NV = 16-byte lane slots per row (ceil(d / 256)): a compile-time trip count keeps every load of a
 // row in flight at once (the generic 8-slot loop with run-time predicates ran at 2.5 TB/s, the LayerNorm kernels at 5.7)
-template <int NV, bool XB = false>      // XB: the residual stream starts in bf16 (x points at bf16 rows): no fp32 copy + cast pass
+// XB: the residual stream starts in bf16 (x points at bf16 rows): no fp32 copy + cast pass.  Pos: PosFull or PosKeep; token
+// tkn > 0 of sample b reads patch row b * (L - 1) + tkn - 1 in both.
+template <int NV, bool XB, class Pos>
 __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
-                                                           const float* __restrict__ pos, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, float* __restrict__ x,
-                                                           float* __restrict__ mean, float* __restrict__ rstd, int B,
-                                                           int L, int d, float eps) {
+                                                           const float* __restrict__ pos, const Pos pos_row,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ x, float* __restrict__ mean,
+                                                           float* __restrict__ rstd, int B, int L, int d, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (row >= B * L) return;
     const int b = row / L, tkn = row - b * L;
     const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
-    const float* pr = pos + (long long)tkn * d;
+    const float* pr = pos + (long long)pos_row(b, L, tkn) * d;
     const int nv = d >> 2;
     f32x4 v[NV];
     float s = 0.f;
@@ -117,24 +143,20 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restri
             f32x4 o;
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = (v[i][c] - mu) * rs * g[c] + bb[c];
-            if (XB) {
-                bf16x4 ob;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) ob[c] = (bf16)o[c];
-                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(x) + (long long)row * d + e * 4) = ob;
-            } else {
-                st4(x + (long long)row * d + e * 4, o);
-            }
+            if (XB) stbf4(reinterpret_cast<bf16*>(x) + (long long)row * d + e * 4, o);
+            else st4(x + (long long)row * d + e * 4, o);
         }
     }
 }
 
-template <int NV>
+// LN backward of the same rows; every workgroup leaves its partial dgamma / dbeta in partial[blockIdx.x][2][d]
+template <int NV, class Pos>
 __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(float* __restrict__ dres, const float* __restrict__ patch,
                                                            const float* __restrict__ cls, const float* __restrict__ pos,
-                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                           const float* __restrict__ gamma, bf16* __restrict__ dpatch,
-                                                           float* __restrict__ partial, int B, int L, int d) {
+                                                           const Pos pos_row, const float* __restrict__ mean,
+                                                           const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                           bf16* __restrict__ dpatch, float* __restrict__ partial, int B,
+                                                           int L, int d) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // uniform: row pointers in SGPRs
     const int nv = d >> 2;
@@ -149,7 +171,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(float* __restrict__ d
     for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
         const int b = row / L, tkn = row - b * L;
         const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
-        const float* pr = pos + (long long)tkn * d;
+        const float* pr = pos + (long long)pos_row(b, L, tkn) * d;
         const float mu = mean[row], rs = rstd[row];
         float* dr = dres + (long long)row * d;
         f32x4 g[NV], xh[NV];
@@ -181,11 +203,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(float* __restrict__ d
 #pragma unroll
                 for (int c = 0; c < 4; ++c) o[c] = rs * (g[i][c] - s1 - xh[i][c] * s2);
                 st4(dr + e * 4, o);
-                if (tkn > 0) {
-                    bf16x4 ob;
-                    ob[0] = (bf16)o[0]; ob[1] = (bf16)o[1]; ob[2] = (bf16)o[2]; ob[3] = (bf16)o[3];
-                    *reinterpret_cast<bf16x4*>(dpatch + ((long long)b * (L - 1) + (tkn - 1)) * d + e * 4) = ob;
-                }
+                if (tkn > 0) stbf4(dpatch + ((long long)b * (L - 1) + (tkn - 1)) * d + e * 4, o);
             }
         }
     }
@@ -231,8 +249,9 @@ __global__ __launch_bounds__(1024) void colvec2_finalize_kernel(const float* __r
     }
 }
 
-// out[i] = sum_b x[b*n + i], i < n (n = L*d), float4 lanes
-__global__ void batch_sum_kernel(const float* __restrict__ x, float* __restrict__ out, int B, long long n4) {
+// out[i] = sum_b x[b*n + i], i < n (n = L*d), float4 lanes; head (may be null) also receives the first head4 of them
+__global__ void batch_sum_kernel(const float* __restrict__ x, float* __restrict__ out, float* __restrict__ head, int B,
+                                 long long n4, int head4) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
     f32x4 p[4];
@@ -244,7 +263,57 @@ __global__ void batch_sum_kernel(const float* __restrict__ x, float* __restrict_
         for (int u = 0; u < 4; ++u) p[u] += reinterpret_cast<const f32x4*>(x)[(long long)(b + u) * n4 + i];
     }
     for (int u = 0; b < B; ++b, ++u) p[u & 3] += reinterpret_cast<const f32x4*>(x)[(long long)b * n4 + i];
-    reinterpret_cast<f32x4*>(out)[i] = (p[0] + p[1]) + (p[2] + p[3]);
+    const f32x4 s = (p[0] + p[1]) + (p[2] + p[3]);
+    reinterpret_cast<f32x4*>(out)[i] = s;
+    if (head != nullptr && i < head4) reinterpret_cast<f32x4*>(head)[i] = s;
+}
+
+// Run-time width -> the row kernels' NV: calls f(std::integral_constant<int, NV>{}) with NV = ceil(d / 256), 1 <= NV <= MAXV
+// (the entry points refuse wider rows).  A generic lambda names the kernel instance.
+template <class F, int... I>
+void embed_nv_dispatch(int d, F&& f, std::integer_sequence<int, I...>) {
+    const int nv = (d / 4 + 63) / 64;
+    (void)((nv == I + 1 && (f(std::integral_constant<int, I + 1>{}), true)) || ...);
+}
+
+// workgroups of the backward row kernel = partial dgamma / dbeta blocks in its workspace.  4 workgroups of 4 row-waves per CU:
+// one per CU left the HBM-bound row loop latency-bound
+int embed_bwd_blocks(int B, int L) {
+    const int nblk = (B * L + 3) / 4;
+    return nblk > 1024 ? 1024 : nblk;
+}
+
+template <class Pos>
+int embed_ln_fwd_launch(const float* patch_out, const float* cls, const float* pos, Pos pos_row, const float* gamma,
+                        const float* beta, float* x, bool xb, float* mean, float* rstd, int B, int L, int d, float eps,
+                        void* stream) {
+    embed_nv_dispatch(d, [&](auto NV) {
+        auto kernel = xb ? embed_ln_fwd_kernel<NV.value, true, Pos> : embed_ln_fwd_kernel<NV.value, false, Pos>;
+        kernel<<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(patch_out, cls, pos, pos_row, gamma, beta, x, mean, rstd, B, L,
+                                                                 d, eps);
+    }, std::make_integer_sequence<int, MAXV>{});
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// the row kernel and the reduction of its partial dgamma / dbeta; the caller adds d(positional_embedding)
+template <class Pos>
+int embed_ln_bwd_launch(float* dres, const float* patch_out, const float* cls, const float* pos, Pos pos_row, const float* mean,
+                        const float* rstd, const float* gamma, void* dpatch_bf16, float* dgamma, float* dbeta, float* ws, int B,
+                        int L, int d, hipStream_t st) {
+    const int nblk = embed_bwd_blocks(B, L);
+    const size_t lds = (size_t)4 * 2 * d * sizeof(float);
+    embed_nv_dispatch(d, [&](auto NV) {
+        auto kernel = embed_ln_bwd_kernel<NV.value, Pos>;
+        if (lds > 48 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds);
+        kernel<<<nblk, 256, lds, st>>>(dres, patch_out, cls, pos, pos_row, mean, rstd, gamma, (bf16*)dpatch_bf16, ws, B, L, d);
+    }, std::make_integer_sequence<int, MAXV>{});
+    SC_LAUNCH_CHECK();
+    colvec2_finalize_kernel<<<(2 * d + 63) / 64, 1024, 0, st>>>(ws, nblk, d, dgamma, dbeta);
+    SC_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
@@ -271,54 +340,23 @@ extern "C" int sc_im2col(const float* images, void* patches, int B, int C, int H
     return 0;
 }
 
-static int embed_ln_fwd_launch(const float* patch_out, const float* cls, const float* pos, const float* gamma,
-                               const float* beta, float* x, bool xb, float* mean, float* rstd, int B, int L, int d, float eps,
-                               void* stream);
-
 extern "C" int sc_embed_ln_fwd(const float* patch_out, const float* cls, const float* pos, const float* gamma,
                                const float* beta, float* x, float* mean, float* rstd, int B, int L, int d, float eps,
                                void* stream) {
     SC_CHECK(B > 0 && L > 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256, "sc_embed_ln_fwd: bad shape B=%d L=%d d=%d", B, L, d);
-    return embed_ln_fwd_launch(patch_out, cls, pos, gamma, beta, x, false, mean, rstd, B, L, d, eps, stream);
+    return embed_ln_fwd_launch(patch_out, cls, pos, PosFull{}, gamma, beta, x, false, mean, rstd, B, L, d, eps, stream);
 }
 
 extern "C" int sc_embed_ln_fwd_x16(const float* patch_out, const float* cls, const float* pos, const float* gamma,
                                    const float* beta, void* x_bf16, float* mean, float* rstd, int B, int L, int d, float eps,
                                    void* stream) {
     SC_CHECK(B > 0 && L > 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && x_bf16 != nullptr, "sc_embed_ln_fwd_x16: bad shape B=%d L=%d d=%d", B, L, d);
-    return embed_ln_fwd_launch(patch_out, cls, pos, gamma, beta, (float*)x_bf16, true, mean, rstd, B, L, d, eps, stream);
+    return embed_ln_fwd_launch(patch_out, cls, pos, PosFull{}, gamma, beta, (float*)x_bf16, true, mean, rstd, B, L, d, eps,
+                               stream);
 }
 
-static int embed_ln_fwd_launch(const float* patch_out, const float* cls, const float* pos, const float* gamma,
-                               const float* beta, float* x, bool xb, float* mean, float* rstd, int B, int L, int d, float eps,
-                               void* stream) {
-#define SC_EMBED_FWD(NV)                                                                                                          \
-    do {                                                                                                                          \
-        if (xb) embed_ln_fwd_kernel<NV, true><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(patch_out, cls, pos, gamma, beta, \
-                                                                                                 x, mean, rstd, B, L, d, eps);     \
-        else embed_ln_fwd_kernel<NV, false><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(patch_out, cls, pos, gamma, beta,   \
-                                                                                               x, mean, rstd, B, L, d, eps);     \
-    } while (0)
-    switch ((d / 4 + 63) / 64) {
-        case 1: SC_EMBED_FWD(1); break;
-        case 2: SC_EMBED_FWD(2); break;
-        case 3: SC_EMBED_FWD(3); break;
-        case 4: SC_EMBED_FWD(4); break;
-        case 5: SC_EMBED_FWD(5); break;
-        case 6: SC_EMBED_FWD(6); break;
-        case 7: SC_EMBED_FWD(7); break;
-        default: SC_EMBED_FWD(8); break;
-    }
-#undef SC_EMBED_FWD
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" long long sc_embed_ln_bwd_ws_floats(int B, int L, int d) {
-    int nblk = (B * L + 3) / 4;
-    if (nblk > 1024) nblk = 1024;      // 4 workgroups of 4 row-waves per CU: one per CU left the HBM-bound row loop latency-bound
-    return (long long)nblk * 2 * d;
-}
+// the one place that sizes the workspace: embed_ln_bwd_launch writes embed_bwd_blocks(B, L) blocks of 2 * d floats into it
+extern "C" long long sc_embed_ln_bwd_ws_floats(int B, int L, int d) { return (long long)embed_bwd_blocks(B, L) * 2 * d; }
 
 extern "C" int sc_embed_ln_bwd(float* dres, const float* patch_out, const float* cls, const float* pos,
                                const float* mean, const float* rstd, const float* gamma, void* dpatch_bf16,
@@ -326,36 +364,13 @@ extern "C" int sc_embed_ln_bwd(float* dres, const float* patch_out, const float*
                                void* stream) {
     SC_CHECK(B > 0 && L > 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256, "sc_embed_ln_bwd: bad shape B=%d L=%d d=%d", B, L, d);
     hipStream_t st = (hipStream_t)stream;
-    int nblk = (B * L + 3) / 4;
-    if (nblk > 1024) nblk = 1024;      // 4 workgroups of 4 row-waves per CU: one per CU left the HBM-bound row loop latency-bound
-    const size_t lds = (size_t)4 * 2 * d * sizeof(float);
-#define SC_EMBED_BWD(NV)                                                                                              \
-    do {                                                                                                              \
-        if (lds > 48 * 1024)                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_ln_bwd_kernel<NV>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
-        embed_ln_bwd_kernel<NV><<<nblk, 256, lds, st>>>(dres, patch_out, cls, pos, mean, rstd, gamma,                  \
-                                                        (bf16*)dpatch_bf16, ws, B, L, d);                             \
-    } while (0)
-    switch ((d / 4 + 63) / 64) {
-        case 1: SC_EMBED_BWD(1); break;
-        case 2: SC_EMBED_BWD(2); break;
-        case 3: SC_EMBED_BWD(3); break;
-        case 4: SC_EMBED_BWD(4); break;
-        case 5: SC_EMBED_BWD(5); break;
-        case 6: SC_EMBED_BWD(6); break;
-        case 7: SC_EMBED_BWD(7); break;
-        default: SC_EMBED_BWD(8); break;
-    }
-#undef SC_EMBED_BWD
-    SC_LAUNCH_CHECK();
-    colvec2_finalize_kernel<<<(2 * d + 63) / 64, 1024, 0, st>>>(ws, nblk, d, dgamma, dbeta);
-    SC_LAUNCH_CHECK();
+    const int rc = embed_ln_bwd_launch(dres, patch_out, cls, pos, PosFull{}, mean, rstd, gamma, dpatch_bf16, dgamma, dbeta, ws,
+                                       B, L, d, st);
+    if (rc != 0) return rc;
+    // d(class_embedding) = d(token row 0) summed over the batch = dpos[0]: the same sums, stored a second time
     const long long n4 = (long long)L * d / 4;
-    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, B, n4);
+    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, dcls, B, n4, d / 4);
     SC_LAUNCH_CHECK();
-    // d(class_embedding) = d(token row 0) summed over the batch = dpos[0]
-    (void)hipMemcpyAsync(dcls, dpos, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, st);
     return 0;
 }
 
@@ -507,11 +522,7 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int* __
     const f32x4 v = ld4(src + (long long)b * d + e);
     const long long row = (long long)b * L + idx[b];
     st4(dst + row * d + e, v);
-    if (dst_bf) {
-        bf16x4 o;
-        o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
-        *reinterpret_cast<bf16x4*>(dst_bf + row * d + e) = o;
-    }
+    if (dst_bf) stbf4(dst_bf + row * d + e, v);
 }
 
 }  // namespace
@@ -538,7 +549,7 @@ extern "C" int sc_token_embed_bwd(const long long* tokens, const float* dres, fl
     token_embed_bwd_kernel<<<blocks, 256, 0, st>>>(tokens, dres, dtable, B * L, d, V);
     SC_LAUNCH_CHECK();
     const long long n4 = (long long)L * d / 4;
-    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, B, n4);
+    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, nullptr, B, n4, 0);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -557,7 +568,7 @@ extern "C" int sc_token_embed_bwd_det(const long long* tokens, const int* eot, c
     token_embed_bwd_det_kernel<<<(npairs + 7) / 8, 512, lds, st>>>(tokens, eot, dres, dtable, rows, L, d, V, nslab, npairs);
     SC_LAUNCH_CHECK();
     const long long n4 = (long long)L * d / 4;
-    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, B, n4);
+    batch_sum_kernel<<<(int)((n4 + 255) / 256), 256, 0, st>>>(dres, dpos, nullptr, B, n4, 0);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -589,9 +600,9 @@ extern "C" int sc_scatter_rows_f32(const float* src, const int* idx, int L, floa
 // training forward keeps K of the n patch tokens of every image plus the class token.  Here the K kept patches are chosen on
 // the device (sc_patch_keep), kept in ASCENDING patch order (the class-token feature and every gradient are invariant to the
 // token order: the positions are added before the drop), and only those are im2col'd, embedded and normalised; the backward
-// sends d(positional_embedding) back to the kept positions through the inverse map ``slot``.  The kernels of the full-length
-// path above are untouched; the per-row arithmetic below is theirs, expression by expression (a kept row is bit-identical
-// to the full kernel's row).
+// sends d(positional_embedding) back to the kept positions through the inverse map ``slot``.  The row kernels are the
+// full-length pass's own (embed_ln_fwd_kernel / embed_ln_bwd_kernel with PosKeep), so a kept row is bit-identical to that
+// row of a full pass; what is separate here is the selection, the im2col walks and d(positional_embedding).
 namespace {
 
 SC_DEVICE unsigned mix32(unsigned h) {      // murmur3's 32-bit finaliser
@@ -633,11 +644,6 @@ __global__ __launch_bounds__(256) void patch_keep_kernel(int* __restrict__ keep,
     }
 }
 
-SC_DEVICE int keep_at(const int* __restrict__ keep, long long i, int n) {      // a foreign index never leaves the tables
-    const int j = keep[i];
-    return j < 0 ? 0 : (j >= n ? n - 1 : j);
-}
-
 // im2col of the kept patches, generic patch size: one thread per (kept row, c, py) copies P pixels (im2col_kernel's walk)
 __global__ void im2col_keep_kernel(const float* __restrict__ img, const int* __restrict__ keep, bf16* __restrict__ out, int B,
                                    int K, int C, int H, int W, int P, long long ld_out) {
@@ -653,16 +659,7 @@ __global__ void im2col_keep_kernel(const float* __restrict__ img, const int* __r
         const int gy = j / G_w, gx = j - gy * G_w;
         const float* src = img + (((long long)b * C + c) * H + gy * P + py) * W + gx * P;
         bf16* dst = out + r * ld_out + (c * P + py) * P;
-        if ((P & 3) == 0 && (W & 3) == 0) {
-            for (int x = 0; x < P; x += 4) {
-                const f32x4 v = ld4(src + x);
-                bf16x4 o;
-                o[0] = (bf16)v[0]; o[1] = (bf16)v[1]; o[2] = (bf16)v[2]; o[3] = (bf16)v[3];
-                *reinterpret_cast<bf16x4*>(dst + x) = o;
-            }
-        } else {
-            for (int x = 0; x < P; ++x) dst[x] = (bf16)src[x];
-        }
+        copy_pixel_run(src, dst, P, W);
     }
 }
 
@@ -684,147 +681,8 @@ __global__ __launch_bounds__(256) void im2col_keep_chunk_kernel(const float* __r
         const int j = keep_at(keep, r, n);
         const int gy = j / G_w, gx = j - gy * G_w;
         const float* src = img + (((long long)b * C + c) * H + gy * P + py) * W + gx * P + px0;
-        const f32x4 v0 = ld4(src), v1 = ld4(src + 4);
-        bf16x8 o;
-        o[0] = (bf16)v0[0]; o[1] = (bf16)v0[1]; o[2] = (bf16)v0[2]; o[3] = (bf16)v0[3];
-        o[4] = (bf16)v1[0]; o[5] = (bf16)v1[1]; o[6] = (bf16)v1[2]; o[7] = (bf16)v1[3];
-        *reinterpret_cast<bf16x8*>(out + r * ld_out + (long long)q * 8) = o;
+        *reinterpret_cast<bf16x8*>(out + r * ld_out + (long long)q * 8) = sc_cat(bf4(ld4(src)), bf4(ld4(src + 4)));
     }
-}
-
-// embed_ln_fwd_kernel with the position row looked up: token t > 0 of sample b reads patch row b * K + t - 1 (K = L - 1, as in
-// the full kernel with L tokens) and position keep[b, t - 1] + 1
-template <int NV, bool XB = false>
-__global__ __launch_bounds__(256) void embed_ln_fwd_keep_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
-                                                                const float* __restrict__ pos, const int* __restrict__ keep,
-                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                float* __restrict__ x, float* __restrict__ mean,
-                                                                float* __restrict__ rstd, int B, int L, int n, int d, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (row >= B * L) return;
-    const int b = row / L, tkn = row - b * L;
-    const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
-    const int ptk = tkn == 0 ? 0 : keep_at(keep, (long long)b * (L - 1) + (tkn - 1), n) + 1;
-    const float* pr = pos + (long long)ptk * d;
-    const int nv = d >> 2;
-    f32x4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int e = i * 64 + lane;
-        if (e < nv) {
-            v[i] = ld4(src + e * 4) + ld4(pr + e * 4);
-            s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-        }
-    }
-    const float mu = sc_wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int e = i * 64 + lane;
-        if (e < nv) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const float u = v[i][c] - mu; q += u * u; }
-        }
-    }
-    const float rs = rsqrtf(sc_wave_sum(q) / (float)d + eps);
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int e = i * 64 + lane;
-        if (e < nv) {
-            const f32x4 g = ld4(gamma + e * 4), bb = ld4(beta + e * 4);
-            f32x4 o;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) o[c] = (v[i][c] - mu) * rs * g[c] + bb[c];
-            if (XB) {
-                bf16x4 ob;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) ob[c] = (bf16)o[c];
-                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16*>(x) + (long long)row * d + e * 4) = ob;
-            } else {
-                st4(x + (long long)row * d + e * 4, o);
-            }
-        }
-    }
-}
-
-// embed_ln_bwd_kernel with the position row looked up (same row loop, same partial sums of dgamma / dbeta)
-template <int NV>
-__global__ __launch_bounds__(256) void embed_ln_bwd_keep_kernel(float* __restrict__ dres, const float* __restrict__ patch,
-                                                                const float* __restrict__ cls, const float* __restrict__ pos,
-                                                                const int* __restrict__ keep, const float* __restrict__ mean,
-                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                                bf16* __restrict__ dpatch, float* __restrict__ partial, int B,
-                                                                int L, int n, int d) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nv = d >> 2;
-    const int rows = B * L;
-    f32x4 ag[NV], ab[NV], gm[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        ag[i] = ab[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const int e = i * 64 + lane;
-        gm[i] = e < nv ? ld4(gamma + e * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
-        const int b = row / L, tkn = row - b * L;
-        const float* src = tkn == 0 ? cls : patch + ((long long)b * (L - 1) + (tkn - 1)) * d;
-        const int ptk = tkn == 0 ? 0 : keep_at(keep, (long long)b * (L - 1) + (tkn - 1), n) + 1;
-        const float* pr = pos + (long long)ptk * d;
-        const float mu = mean[row], rs = rstd[row];
-        float* dr = dres + (long long)row * d;
-        f32x4 g[NV], xh[NV];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int e = i * 64 + lane;
-            if (e < nv) {
-                const f32x4 dyv = ld4(dr + e * 4);
-                const f32x4 xv = ld4(src + e * 4) + ld4(pr + e * 4);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    xh[i][c] = (xv[c] - mu) * rs;
-                    g[i][c] = dyv[c] * gm[i][c];
-                    s1 += g[i][c];
-                    s2 += g[i][c] * xh[i][c];
-                    ag[i][c] += dyv[c] * xh[i][c];
-                    ab[i][c] += dyv[c];
-                }
-            }
-        }
-        s1 = sc_wave_sum(s1) / (float)d;
-        s2 = sc_wave_sum(s2) / (float)d;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int e = i * 64 + lane;
-            if (e < nv) {
-                f32x4 o;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = rs * (g[i][c] - s1 - xh[i][c] * s2);
-                st4(dr + e * 4, o);
-                if (tkn > 0) {
-                    bf16x4 ob;
-                    ob[0] = (bf16)o[0]; ob[1] = (bf16)o[1]; ob[2] = (bf16)o[2]; ob[3] = (bf16)o[3];
-                    *reinterpret_cast<bf16x4*>(dpatch + ((long long)b * (L - 1) + (tkn - 1)) * d + e * 4) = ob;
-                }
-            }
-        }
-    }
-    float* sm = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int e = i * 64 + lane;
-        if (e < nv) {
-            st4(sm + (wave * 2 + 0) * d + e * 4, ag[i]);
-            st4(sm + (wave * 2 + 1) * d + e * 4, ab[i]);
-        }
-    }
-    __syncthreads();
-    float* pout = partial + (long long)blockIdx.x * 2 * d;
-    for (int e = threadIdx.x; e < 2 * d; e += 256) pout[e] = sm[e] + sm[2 * d + e] + sm[4 * d + e] + sm[6 * d + e];
 }
 
 // d(positional_embedding) of a dropping pass, one workgroup per position row p (all n + 1 rows are written): row 0 sums the class
@@ -892,37 +750,12 @@ extern "C" int sc_im2col_keep(const float* images, const int* keep, void* patche
     return 0;
 }
 
-static int embed_ln_fwd_keep_launch(const float* patch_out, const float* cls, const float* pos, const int* keep,
-                                    const float* gamma, const float* beta, float* x, bool xb, float* mean, float* rstd, int B,
-                                    int L, int n, int d, float eps, void* stream) {
-#define SC_EMBED_FWD_KEEP(NV)                                                                                                      \
-    do {                                                                                                                          \
-        if (xb) embed_ln_fwd_keep_kernel<NV, true><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(                             \
-            patch_out, cls, pos, keep, gamma, beta, x, mean, rstd, B, L, n, d, eps);                                              \
-        else embed_ln_fwd_keep_kernel<NV, false><<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(                               \
-            patch_out, cls, pos, keep, gamma, beta, x, mean, rstd, B, L, n, d, eps);                                              \
-    } while (0)
-    switch ((d / 4 + 63) / 64) {
-        case 1: SC_EMBED_FWD_KEEP(1); break;
-        case 2: SC_EMBED_FWD_KEEP(2); break;
-        case 3: SC_EMBED_FWD_KEEP(3); break;
-        case 4: SC_EMBED_FWD_KEEP(4); break;
-        case 5: SC_EMBED_FWD_KEEP(5); break;
-        case 6: SC_EMBED_FWD_KEEP(6); break;
-        case 7: SC_EMBED_FWD_KEEP(7); break;
-        default: SC_EMBED_FWD_KEEP(8); break;
-    }
-#undef SC_EMBED_FWD_KEEP
-    SC_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int sc_embed_ln_fwd_keep(const float* patch_out, const float* cls, const float* pos, const int* keep,
                                     const float* gamma, const float* beta, float* x, float* mean, float* rstd, int B, int L,
                                     int n, int d, float eps, void* stream) {
     SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr,
              "sc_embed_ln_fwd_keep: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
-    return embed_ln_fwd_keep_launch(patch_out, cls, pos, keep, gamma, beta, x, false, mean, rstd, B, L, n, d, eps, stream);
+    return embed_ln_fwd_launch(patch_out, cls, pos, PosKeep{keep, n}, gamma, beta, x, false, mean, rstd, B, L, d, eps, stream);
 }
 
 extern "C" int sc_embed_ln_fwd_keep_x16(const float* patch_out, const float* cls, const float* pos, const int* keep,
@@ -930,8 +763,8 @@ extern "C" int sc_embed_ln_fwd_keep_x16(const float* patch_out, const float* cls
                                         int L, int n, int d, float eps, void* stream) {
     SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr && x_bf16 != nullptr,
              "sc_embed_ln_fwd_keep_x16: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
-    return embed_ln_fwd_keep_launch(patch_out, cls, pos, keep, gamma, beta, (float*)x_bf16, true, mean, rstd, B, L, n, d, eps,
-                                    stream);
+    return embed_ln_fwd_launch(patch_out, cls, pos, PosKeep{keep, n}, gamma, beta, (float*)x_bf16, true, mean, rstd, B, L, d,
+                               eps, stream);
 }
 
 extern "C" int sc_embed_ln_bwd_keep(float* dres, const float* patch_out, const float* cls, const float* pos, const int* keep,
@@ -941,31 +774,9 @@ extern "C" int sc_embed_ln_bwd_keep(float* dres, const float* patch_out, const f
     SC_CHECK(B > 0 && L > 1 && L <= n + 1 && d > 0 && (d % 4) == 0 && d <= MAXV * 256 && keep != nullptr && slot != nullptr,
              "sc_embed_ln_bwd_keep: bad shape B=%d L=%d n=%d d=%d", B, L, n, d);
     hipStream_t st = (hipStream_t)stream;
-    int nblk = (B * L + 3) / 4;
-    if (nblk > 1024) nblk = 1024;      // the workspace of sc_embed_ln_bwd_ws_floats(B, L, d)
-    const size_t lds = (size_t)4 * 2 * d * sizeof(float);
-#define SC_EMBED_BWD_KEEP(NV)                                                                                         \
-    do {                                                                                                              \
-        if (lds > 48 * 1024)                                                                                          \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_ln_bwd_keep_kernel<NV>),                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
-        embed_ln_bwd_keep_kernel<NV><<<nblk, 256, lds, st>>>(dres, patch_out, cls, pos, keep, mean, rstd, gamma,      \
-                                                             (bf16*)dpatch_bf16, ws, B, L, n, d);                     \
-    } while (0)
-    switch ((d / 4 + 63) / 64) {
-        case 1: SC_EMBED_BWD_KEEP(1); break;
-        case 2: SC_EMBED_BWD_KEEP(2); break;
-        case 3: SC_EMBED_BWD_KEEP(3); break;
-        case 4: SC_EMBED_BWD_KEEP(4); break;
-        case 5: SC_EMBED_BWD_KEEP(5); break;
-        case 6: SC_EMBED_BWD_KEEP(6); break;
-        case 7: SC_EMBED_BWD_KEEP(7); break;
-        default: SC_EMBED_BWD_KEEP(8); break;
-    }
-#undef SC_EMBED_BWD_KEEP
-    SC_LAUNCH_CHECK();
-    colvec2_finalize_kernel<<<(2 * d + 63) / 64, 1024, 0, st>>>(ws, nblk, d, dgamma, dbeta);
-    SC_LAUNCH_CHECK();
+    const int rc = embed_ln_bwd_launch(dres, patch_out, cls, pos, PosKeep{keep, n}, mean, rstd, gamma, dpatch_bf16, dgamma, dbeta,
+                                       ws, B, L, d, st);
+    if (rc != 0) return rc;
     dpos_keep_kernel<<<n + 1, 256, 0, st>>>(dres, slot, dpos, dcls, B, L, n, d);
     SC_LAUNCH_CHECK();
     return 0;

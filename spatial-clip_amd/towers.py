@@ -727,9 +727,18 @@ class PatchTransformerTower:
                                       int(width * mlp_ratio), causal=False, cls_only_last=True, res16_ok=True,
                                       quick_gelu=self.quick_gelu)
         self.bufs = _Bufs(store.device)
+        # state of the last forward, read by its backward: the token count of THAT pass (K + 1 when patches were dropped) and
+        # its (keep [B, K], slot [B, n]) pair, (None, None) for a full-length pass (set by _patchify: VisionTower)
+        self.L_run = tokens
+        self._keep = (None, None)
+        self._pad_zeroed: Dict[str, torch.Tensor] = {}      # patch buffer name -> the tensor whose K padding is zeroed
 
     def _n(self, leaf: str) -> str:
         return self.prefix + leaf
+
+    def _name_pass_bufs(self) -> None:
+        """The activations of a dropping pass live under buffer names of their own."""
+        self.bufs.suffix = self.stack.bufs.suffix = "" if self._keep[0] is None else ".keep"
 
     def param_names_head(self) -> List[str]:
         return [self._n("ln_post.weight"), self._n("ln_post.bias"), self._n("proj")]
@@ -745,14 +754,11 @@ class PatchTransformerTower:
     def forward(self, inp: torch.Tensor) -> torch.Tensor:
         s, d, D = self.s, self.d, self.D
         s.wait_names(self.param_names_stem())
-        self._keep = None             # (keep [B, K], slot [B, n]) of a dropping pass: set by _patchify (VisionTower)
-        self.bufs.suffix = self.stack.bufs.suffix = ""
+        self._keep = (None, None)
+        self._name_pass_bufs()
         patches = self._patchify(inp)
-        B = self.B
-        keep = self._keep[0] if self._keep is not None else None
-        # effective token count of THIS pass: K + 1 when patches are dropped; its activations live under their own buffer names
+        B, keep = self.B, self._keep[0]
         L = self.L_run = self.L if keep is None else keep.shape[1] + 1
-        self.bufs.suffix = self.stack.bufs.suffix = "" if keep is None else ".keep"
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
         patch_out = bf.get("patch_out", (Mp, d), F32)
@@ -785,9 +791,9 @@ class PatchTransformerTower:
     def backward(self, d_f: torch.Tensor, on_bucket: Optional[Callable[[List[str]], None]] = None) -> None:
         s, d, D, B = self.s, self.d, self.D, self.B
         # the token count and the buffers of the forward this backward belongs to (K + 1 tokens after a dropping forward)
-        L = getattr(self, "L_run", self.L)
-        keep, slot = self._keep if getattr(self, "_keep", None) is not None else (None, None)
-        self.bufs.suffix = self.stack.bufs.suffix = "" if keep is None else ".keep"
+        L = self.L_run
+        keep, slot = self._keep
+        self._name_pass_bufs()
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
         d_raw = bf.get("d_raw", (B, D), BF16)
@@ -875,19 +881,15 @@ class VisionTower(PatchTransformerTower):
         self.B = B = images.shape[0]
         drop, self.drop = self.drop, None               # armed for ONE forward
         if drop is not None and self.patch_dropout > 0.0:
-            keep, slot = self._select(B, drop)
-            self._keep = (keep, slot)
-            patches = self.bufs.get("patches.keep", (B * keep.shape[1], self.kp_pad), BF16)
-            if self.kp_pad != self.kp and getattr(self, "_pad_zeroed_keep", None) is not patches:
-                patches.zero_()        # as below: the K padding must be finite zeros
-                self._pad_zeroed_keep = patches
-            ops.im2col(images, patches, v.patch_size, keep=keep)
-            return patches
-        patches = self.bufs.get("patches", (B * (self.L - 1), self.kp_pad), BF16)
-        if self.kp_pad != self.kp and getattr(self, "_pad_zeroed", None) is not patches:
+            self._keep = self._select(B, drop)
+            self._name_pass_bufs()
+        keep = self._keep[0]
+        name = "patches" + self.bufs.suffix
+        patches = self.bufs.get("patches", (B * (self.L - 1 if keep is None else keep.shape[1]), self.kp_pad), BF16)
+        if self.kp_pad != self.kp and self._pad_zeroed.get(name) is not patches:
             patches.zero_()            # the K padding must be finite zeros; im2col only writes the real columns
-            self._pad_zeroed = patches
-        ops.im2col(images, patches, v.patch_size)
+            self._pad_zeroed[name] = patches
+        ops.im2col(images, patches, v.patch_size, keep=keep)
         return patches
 
 

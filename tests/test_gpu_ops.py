@@ -413,10 +413,17 @@ def test_colsum_l2norm_casts():
     assert torch.equal(dt.cpu(), bf(w).t())
 
 
-@pytest.mark.parametrize("P,S,d", [(8, 32, 64), (16, 224, 192), (14, 224, 64), (16, 64, 768), (8, 32, 1024), (16, 48, 1280)])
-def test_im2col_embed(P, S, d):
+# every NV instance (ceil(d / 256) = 1..8) of the full-length stem kernels: d = 260 / 2044 leave the last lane slot almost
+# empty / one short, d = 2048 takes the backward past 48 KiB of LDS; B = 120 at 37 tokens is 4440 rows, more than the 4096 that
+# the backward's 1024 capped workgroups take in one round (its grid-stride loop)
+_EMBED_CASES = [(8, 32, 64), (16, 224, 192), (14, 224, 64), (16, 64, 768), (8, 32, 1024), (16, 48, 1280)] + \
+               [(8, 16, d) for d in (256, 260, 512, 1536, 1792, 2044, 2048)]
+
+
+@pytest.mark.parametrize("P,S,d,B", [pytest.param(*c, 3, id="-".join(map(str, c))) for c in _EMBED_CASES]
+                         + [pytest.param(8, 48, 64, 120, id="8-48-64-B120")])
+def test_im2col_embed(P, S, d, B):
     ops = _ops()
-    B = 3
     g = torch.Generator().manual_seed(P)
     img = torch.randn(B, 3, S, S, generator=g)
     G_ = S // P
@@ -439,6 +446,12 @@ def test_im2col_embed(P, S, d):
     x = torch.empty(B * L, d, device="cuda"); mean = torch.empty(B * L, device="cuda"); rstd = torch.empty(B * L, device="cuda")
     ops.embed_ln_fwd(patch_out.cuda(), cls.cuda(), pos.cuda(), gamma.cuda(), beta.cuda(), x, mean, rstd, B, L, d)
     torch.testing.assert_close(x.cpu(), xref.detach().view(B * L, d), atol=1e-5, rtol=1e-5)
+    # the bf16 residual stream written directly: the fp32 result rounded once, and the same statistics
+    x16 = torch.empty(B * L, d, dtype=torch.bfloat16, device="cuda")
+    mean16 = torch.empty(B * L, device="cuda"); rstd16 = torch.empty(B * L, device="cuda")
+    ops.embed_ln_fwd(patch_out.cuda(), cls.cuda(), pos.cuda(), gamma.cuda(), beta.cuda(), x16, mean16, rstd16, B, L, d)
+    assert torch.equal(x16, x.to(torch.bfloat16))
+    assert torch.equal(mean16, mean) and torch.equal(rstd16, rstd)
     dres = dx.clone().cuda()
     dpatch = torch.empty(B * (L - 1), d, dtype=torch.bfloat16, device="cuda")
     dg = torch.empty(d, device="cuda"); db = torch.empty(d, device="cuda")

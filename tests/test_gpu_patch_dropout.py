@@ -99,9 +99,11 @@ def _forced_keep(B, n, K):
     return keep
 
 
-@pytest.mark.parametrize("B,Lk,d,forced", [(1, 9, 192, False), (3, 9, 768, False), (90, 50, 64, False), (3, 6, 1280, True)])
+@pytest.mark.parametrize("B,Lk,d,forced", [(1, 9, 192, False), (3, 9, 768, False), (90, 50, 64, False), (3, 6, 1280, True),
+                                           (2, 4, 2048, False)])
 def test_embed_ln_bwd_keep_against_the_full_kernel_on_zero_padded_gradients(B, Lk, d, forced):
-    """B = 90, L' = 50: 4500 rows = 1125 row groups, more than the 1024 workgroups of the persistent row loop."""
+    """B = 90, L' = 50: 4500 rows = 1125 row groups, more than the 1024 workgroups of the persistent row loop.  d = 2048: the
+    workgroup's 64 KiB of LDS needs the raised dynamic-LDS limit."""
     *_, ops, _, pd = _pkg()
     n = 60
     L, K = n + 1, Lk - 1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel resource and instruction-class table of gfx950 assembly files (hipcc --save-temps leaves one *.s per source):
-VGPRs, scratch bytes, waves per SIMD, LDS bytes, instruction count, and the counts of v_mfma*, ds_read*, ds_write*,
+VGPRs, SGPRs, scratch bytes, waves per SIMD, LDS bytes, instruction count, and the counts of v_mfma*, ds_read*, ds_write*,
 global_load*, global_store*.  A changed count of one of these between two commits means a kernel's loop body changed.
 An instruction is a line of a kernel's body that is left when comments, labels and directives are dropped.  Kernels are
 the symbols whose mangled name holds `kernel`; names are demangled with binutils' c++filt, which must be on the PATH.
@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 CLASSES = ("v_mfma", "ds_read", "ds_write", "global_load", "global_store")
-FIELDS = ("NumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
+FIELDS = ("TotalNumSgprs", "NumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
 
 
 def kernels(path):
@@ -44,10 +44,10 @@ def main():
         ks.update(kernels(f))
     names = subprocess.run(["c++filt", "-p"], input="\n".join(ks), capture_output=True, text=True, check=True).stdout.split("\n")
     assert len(names) >= len(ks), "c++filt returned fewer names than kernels"
-    print(f"{'VGPR':>4} {'scr':>3} {'wav':>3} {'LDS':>6} {'instr':>5} " + " ".join(f"{c:>12}" for c in CLASSES) + "  kernel")
+    print(f"{'VGPR':>4} {'SGPR':>4} {'scr':>3} {'wav':>3} {'LDS':>6} {'instr':>5} " + " ".join(f"{c:>12}" for c in CLASSES) + "  kernel")
     for (body, res), nm in zip(ks.values(), names):
         n = [sum(i.startswith(c) for i in body) for c in CLASSES]
-        print(f"{res['NumVgprs']:4d} {res['ScratchSize']:3d} {res['Occupancy']:3d} {res['LDSByteSize']:6d} {len(body):5d} "
+        print(f"{res['NumVgprs']:4d} {res['TotalNumSgprs']:4d} {res['ScratchSize']:3d} {res['Occupancy']:3d} {res['LDSByteSize']:6d} {len(body):5d} "
               + " ".join(f"{x:12d}" for x in n) + "  " + nm.replace("(anonymous namespace)::", ""))
 
 
