@@ -303,6 +303,8 @@ extern "C" int sc_gemm_bf16(int mode, int epi, const void* A, int lda, const voi
         g.C = slabs; g.slab_stride = (long long)M * N;
     }
     const int nblocks = g.ntm * g.ntn * splitk;
+    sc_gemm_note_path(mode == SC_GEMM_TN ? SC_GEMM_PATH_TN128 : (K % BK) != 0 ? SC_GEMM_PATH_NT128_KTAIL : SC_GEMM_PATH_NT128, 0, 0,
+                      splitk, SC_GEMM_COLSUM_NONE);
     int rc = -1;
 #define SC_CASE(MODE, EPI) \
     if (mode == MODE && epi == EPI) rc = launch<MODE, EPI>(g, nblocks, st);
@@ -383,6 +385,7 @@ extern "C" int sc_gemm_wgrad_bias(const void* dY, int lddy, const void* X, int l
     int rc = sc_gemm_bf16(SC_GEMM_TN, SC_EPI_F32, dY, lddy, X, ldx, M, N, K, dW, ldw, nullptr, 0, nullptr, nullptr, 0,
                           nullptr, 0, slab_floats ? splitk : 1, slab_floats ? slabs : nullptr, stream);
     if (rc != 0) return rc;
+    sc_gemm_note_colsum(SC_GEMM_COLSUM_SEPARATE);
     return sc_colsum_bf16(dY, lddy, K, M, dbias, cs_part, stream);
 }
 
@@ -506,5 +509,6 @@ extern "C" int sc_gemm_wgrad_group(const sc_wgrad_desc* descs, int n, int K, int
         }
         if (rc != 0) return rc;
     }
+    sc_gemm_note_group(SC_GEMM_GROUP_PER_PROBLEM);
     return 0;
 }

@@ -296,6 +296,8 @@ int sc_gemm256_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs,
         g.slab_stride = (long long)g.M * g.N;
     }
     const int nblocks = g.ntm * g.ntn * splitk;
+    sc_gemm_note_path(mode == SC_GEMM_NT ? SC_GEMM_PATH_NT256 : SC_GEMM_PATH_TN256, 0, 0, splitk,
+                      g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
     int rc = 0;
 #define SC_CASE(MODE, EPI) \
     if (mode == MODE && epi == EPI) rc = launch<MODE, EPI>(g, nblocks, st);

@@ -1522,6 +1522,7 @@ int sc_gemm8p_fp8(int epi, GemmArgs& g, hipStream_t st) {
         const char* sw = getenv("SC_GELU_LUT");
         if (!(sw && sw[0] == '0')) g.gelu_lut = sc_gelu_lut_device(st, g.act);
     }
+    sc_gemm_note_path(SC_GEMM_PATH_FP8_NT, g.gelu_lut != nullptr, 0, 1, SC_GEMM_COLSUM_NONE);
     if (epi == SC_EPI_BF16) return launch_f8<SC_EPI_BF16>(g, nblocks, st);
     if (epi == SC_EPI_BF16_BIAS) return launch_f8<SC_EPI_BF16_BIAS>(g, nblocks, st);
     if (epi == SC_EPI_F32_BIAS_RES) return launch_f8<SC_EPI_F32_BIAS_RES>(g, nblocks, st);
@@ -1569,6 +1570,10 @@ int sc_gemm8p_tn_group_launch(const GemmArgs* g, int n, hipStream_t st) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         attr_done = true;
     }
+    bool sums = false;
+    for (int p = 0; p < n; ++p) sums = sums || g[p].colsum != nullptr;
+    sc_gemm_note_path(SC_GEMM_PATH_TN8P_GROUP, 0, 0, g[0].splitk, sums ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
+    sc_gemm_note_group(SC_GEMM_GROUP_ONE_LAUNCH);
     gemm8p_tn_group_kernel<<<total, 512, LDS_BYTES, st>>>(gg);
     SC_LAUNCH_CHECK();
     return 1;
@@ -1601,6 +1606,7 @@ int sc_gemm8p_tn_fp8(GemmArgs& g, int splitk_req, float* slabs, hipStream_t st) 
                                   LDS_BYTES);
         attr_done = true;
     }
+    sc_gemm_note_path(SC_GEMM_PATH_FP8_TN, 0, 0, splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
     gemm8p_tn_f8_kernel<<<g.ntm * g.ntn * splitk, 512, LDS_BYTES, st>>>(g);
     SC_LAUNCH_CHECK();
     return 1;
@@ -1632,6 +1638,21 @@ extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset) {
     if (rem) *rem = sc_last_tail[1];
     if (reset) sc_last_tail[0] = sc_last_tail[1] = -1;
     return 0;
+}
+
+// The kernel the last GEMM entry point dispatched to (enum sc_gemm_path and the fields of sc_debug_gemm_last_path,
+// sc_kernels.h): host-side bookkeeping for tests, like the record above.
+static int sc_last_path[6] = {SC_GEMM_PATH_NONE, 0, 0, 0, SC_GEMM_COLSUM_NONE, SC_GEMM_GROUP_NONE};
+void sc_gemm_note_path(int path, int lut, int col_group, int splitk, int colsum) {
+    sc_last_path[0] = path; sc_last_path[1] = lut; sc_last_path[2] = col_group; sc_last_path[3] = splitk;
+    sc_last_path[4] = colsum; sc_last_path[5] = SC_GEMM_GROUP_NONE;
+}
+void sc_gemm_note_colsum(int colsum) { sc_last_path[4] = colsum; }
+void sc_gemm_note_group(int group) { sc_last_path[5] = group; }
+extern "C" int sc_debug_gemm_last_path(int* out, int n, int reset) {
+    for (int i = 0; i < n && i < 6; ++i) out[i] = sc_last_path[i];
+    if (reset) sc_gemm_note_path(SC_GEMM_PATH_NONE, 0, 0, 0, SC_GEMM_COLSUM_NONE);
+    return 6;
 }
 
 // workgroup slots of the current device = its CU count (queried once per device)
@@ -1687,6 +1708,7 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     }
     const int nblocks = g.ntm * g.ntn * splitk;
     if (mode == SC_GEMM_TN) {
+        sc_gemm_note_path(SC_GEMM_PATH_TN8P, 0, 0, splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
         return launch_tn(g, nblocks, st);
     }
     // GELU by table: only the non-persistent kernel has LDS to spare for it (the persistent one fills all 160 KiB)
@@ -1697,6 +1719,8 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     // persistent walk of the tile list for the store-only bf16 epilogues once there is more than one round of tiles
     static const bool persist = !(getenv("SC_GEMM_PERSIST") && getenv("SC_GEMM_PERSIST")[0] == '0');
     if (g.gelu_lut == nullptr && persist && splitk == 1 && nblocks >= 1024 && ktiles >= 3) {      // >= 4 rounds of tiles (measured: +7 % at 7 rounds, -3 % at 2.3)
+        if (epi == SC_EPI_BF16 || epi == SC_EPI_BF16_BIAS || epi == SC_EPI_GELU_PAIR || epi == SC_EPI_GELU_GRAD_PAIR)
+            sc_gemm_note_path(SC_GEMM_PATH_NT8P_PERSISTENT, 0, 0, 1, SC_GEMM_COLSUM_NONE);
         if (epi == SC_EPI_BF16) return launch_persistent<SC_EPI_BF16>(g, nblocks, st);
         if (epi == SC_EPI_BF16_BIAS) return launch_persistent<SC_EPI_BF16_BIAS>(g, nblocks, st);
         if (epi == SC_EPI_GELU_PAIR) return launch_persistent<SC_EPI_GELU_PAIR>(g, nblocks, st);      // +1.5 % at 9.2 rounds
@@ -1739,6 +1763,7 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     }
     sc_last_tail[0] = g.tail_first > 0 ? g.tail_first : nblocks;
     sc_last_tail[1] = g.tail_rem;
+    sc_gemm_note_path(SC_GEMM_PATH_NT8P, g.gelu_lut != nullptr, g.col_group, splitk, SC_GEMM_COLSUM_NONE);
     int rc = 0;
 #define SC_CASE(EPI) \
     if (epi == EPI) rc = launch<EPI>(g, grid, st);

@@ -340,6 +340,12 @@ SC_DEVICE void sc_epilogue_store(const float* ep, EpiRegs<EPI>& e, int gm0, int 
     }
 }
 
+// The record behind sc_debug_gemm_last_path (sc_gemm8p.hip).  sc_gemm_note_path starts a new record (a launcher calls it once it
+// knows its kernel); the other two amend the record of the call in progress.
+void sc_gemm_note_path(int path, int lut, int col_group, int splitk, int colsum);
+void sc_gemm_note_colsum(int colsum);
+void sc_gemm_note_group(int group);
+
 // 256x256 LDS-DMA kernel (sc_gemm256.hip): returns 1 if it took the problem, 0 if not eligible, <0 on error
 int sc_gemm256_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, float* c_final, hipStream_t st);
 // 256x256x64 phase-interleaved (ping-pong) kernel, NT only (sc_gemm8p.hip)

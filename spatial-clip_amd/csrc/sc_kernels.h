@@ -23,3 +23,27 @@ extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem);
 // sc_debug_gemm_last_tail: (nfull, rem) of this process's last launch of the non-persistent 256x256 NT kernel ((T, 0): not split;
 // (-1, -1): none since the last reset); reset != 0 clears the record.
 extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset);
+
+// Which kernel the last GEMM entry point of this process (sc_gemm_bf16, sc_gemm_wgrad_bias, sc_gemm_wgrad_group, sc_gemm_fp8*,
+// sc_gemm_wgrad_fp8) dispatched to.  Written by the launchers, host-side bookkeeping only (a few int stores per call); the
+// tests assert with it that a shape reached the kernel they are named for.
+enum sc_gemm_path {
+    SC_GEMM_PATH_NONE = -1,
+    SC_GEMM_PATH_NT128 = 0,        // 128x128 general kernel, K a multiple of 64
+    SC_GEMM_PATH_NT128_KTAIL,      // the same with a partial last K tile
+    SC_GEMM_PATH_TN128,
+    SC_GEMM_PATH_NT8P,             // 256x256 phase-interleaved kernel, one workgroup per tile (its tail split: sc_debug_gemm_last_tail)
+    SC_GEMM_PATH_NT8P_PERSISTENT,  // the persistent tile walk of the same kernel
+    SC_GEMM_PATH_TN8P,
+    SC_GEMM_PATH_TN8P_GROUP,       // sc_gemm_wgrad_group: several problems in one launch
+    SC_GEMM_PATH_NT256,            // two-stage LDS-DMA kernel (SC_GEMM_FORCE=256 only)
+    SC_GEMM_PATH_TN256,
+    SC_GEMM_PATH_FP8_NT,
+    SC_GEMM_PATH_FP8_TN
+};
+enum sc_gemm_colsum { SC_GEMM_COLSUM_NONE = 0, SC_GEMM_COLSUM_FUSED, SC_GEMM_COLSUM_SEPARATE };   // bias-gradient column sums
+enum sc_gemm_group { SC_GEMM_GROUP_NONE = 0, SC_GEMM_GROUP_ONE_LAUNCH, SC_GEMM_GROUP_PER_PROBLEM };   // sc_gemm_wgrad_group
+// sc_debug_gemm_last_path: out[0 .. n) = {path, GELU table attached (0 / 1), column group in effect (0: row-major walk), split-K
+// actually used, sc_gemm_colsum, sc_gemm_group} of the last GEMM call (of the last problem, for a group that ran per problem);
+// path SC_GEMM_PATH_NONE before the first call or after a reset.  reset != 0 clears the record.  Returns the number of fields.
+extern "C" int sc_debug_gemm_last_path(int* out, int n, int reset);

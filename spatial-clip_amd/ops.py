@@ -2,6 +2,7 @@
 Every function enqueues on the current HIP stream and never synchronises."""
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Optional
 
@@ -250,6 +251,30 @@ def gemm_last_tail(reset: bool = False):
     nfull, rem = ctypes.c_int(-1), ctypes.c_int(-1)
     fn(ctypes.byref(nfull), ctypes.byref(rem), int(reset))
     return nfull.value, rem.value
+
+
+# enum sc_gemm_path / sc_gemm_colsum / sc_gemm_group (csrc/sc_kernels.h), in order
+GEMM_PATHS = ("nt128", "nt128_ktail", "tn128", "nt8p", "nt8p_persistent", "tn8p", "tn8p_group", "nt256", "tn256", "fp8_nt",
+              "fp8_tn")
+GEMM_COLSUMS = ("none", "fused", "separate")
+GEMM_GROUPS = ("none", "one_launch", "per_problem")
+GemmPath = collections.namedtuple("GemmPath", "path lut col_group splitk colsum group")
+
+
+def gemm_last_path(reset: bool = False) -> GemmPath:
+    """What the last ``gemm`` / ``gemm_wgrad_bias`` / ``gemm_wgrad_group`` / ``gemm_fp8*`` / ``gemm_wgrad_fp8`` of this process
+    dispatched to: ``path`` (one of ``GEMM_PATHS``; ``"none"`` before the first call or after a ``reset``), ``lut`` (the GELU
+    table was attached), ``col_group`` (column group of the tile walk in effect, 0 = row-major), ``splitk`` (the split-K
+    actually used), ``colsum`` (bias-gradient column sums: ``"fused"`` into the TN kernel, a ``"separate"`` kernel, or
+    ``"none"``) and ``group`` (``gemm_wgrad_group``: ``"one_launch"``, or ``"per_problem"`` with the other fields those of the
+    last problem; ``"none"`` for the other entry points).  Whether the 256x256 NT kernel split its tail is
+    ``gemm_last_tail``'s.  A debug hook (``sc_debug_gemm_last_path``): host-side bookkeeping, no device work."""
+    fn = getattr(_lib.lib(), "sc_debug_gemm_last_path")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int]
+    out = (ctypes.c_int * 6)()
+    assert fn(out, 6, int(reset)) == 6
+    return GemmPath(GEMM_PATHS[out[0]] if out[0] >= 0 else "none", bool(out[1]), out[2], out[3], GEMM_COLSUMS[out[4]],
+                    GEMM_GROUPS[out[5]])
 
 
 # ------------------------------------------------------------------------------------------ norms

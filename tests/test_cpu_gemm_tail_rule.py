@@ -33,3 +33,19 @@ def test_rule_properties_over_a_sweep():
                 assert nfull + 2 * rem <= (T // S) * S + S            # the half tiles fit in one round of slots
             else:
                 assert T <= S or T % S == 0 or 2 * (T % S) > S
+
+
+def test_last_path_record_names_match_the_enums():
+    """``ops.gemm_last_path`` without a GPU: no launch yet, so the record is empty, and the name tables have one entry per
+    value of enum sc_gemm_path / sc_gemm_colsum / sc_gemm_group (csrc/sc_kernels.h)."""
+    import os
+    import re
+    p = ops.gemm_last_path(reset=True)
+    assert p == ops.GemmPath("none", False, 0, 0, "none", "none") and ops.gemm_last_path() == p
+    src = open(os.path.join(os.path.dirname(ops.__file__), "csrc", "sc_kernels.h")).read()
+    for enum, prefix, names in (("sc_gemm_path", "SC_GEMM_PATH_", ("none",) + ops.GEMM_PATHS),
+                                ("sc_gemm_colsum", "SC_GEMM_COLSUM_", ops.GEMM_COLSUMS),
+                                ("sc_gemm_group", "SC_GEMM_GROUP_", ops.GEMM_GROUPS)):
+        body = re.search(r"enum %s \{(.*?)\};" % enum, src, re.S).group(1)
+        body = re.sub(r"//[^\n]*", "", body)
+        assert tuple(n.lower() for n in re.findall(prefix + r"(\w+)", body)) == names, enum

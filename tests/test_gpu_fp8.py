@@ -104,6 +104,31 @@ def test_gemm_fp8_is_exact_on_representable_data(M, N, K):
     torch.testing.assert_close(ob.float().cpu(), uref, atol=2e-2, rtol=1e-2)
 
 
+@pytest.mark.parametrize("K", [128 * n for n in (1, 2, 3, 4, 5, 7, 9, 16)])
+def test_gemm_fp8_ring_exact(K):
+    """The e4m3 twin of test_nt_phase_interleaved_ring_exact: the e4m3 NT kernel runs the bf16 kernel's eight-slot LDS ring with
+    K tiles of 128 bytes.  K sweeps 1..16 of them (prologue only, odd and even counts, the ring wrapped more than once), M and N
+    ragged (4 x 3 tiles: this kernel has no size threshold), fresh data each repetition.  Integers in [-7, 7] times
+    power-of-two row scales make every product and partial sum exact in fp32 (|sum| <= 49 K = 100 352 units < 2^24), so the
+    result must equal the float64 product bit for bit: a fragment read from a stale or half-landed slot cannot hide."""
+    ops = _ops()
+    M, N = 256 * 3 + 40, 256 * 2 + 24
+    g = torch.Generator(device="cuda").manual_seed(K)
+    for rep in range(4):
+        a = torch.randint(-7, 8, (M, K), generator=g, device="cuda").float()
+        b = torch.randint(-7, 8, (N, K), generator=g, device="cuda").float()
+        a *= torch.pow(2.0, torch.randint(-3, 4, (M, 1), generator=g, device="cuda").float())
+        b *= torch.pow(2.0, torch.randint(-3, 4, (N, 1), generator=g, device="cuda").float())
+        a8, sa = ops.quantize_rows_fp8(a)
+        b8, sb = ops.quantize_rows_fp8(b)
+        assert torch.equal(deq(a8, sa), a) and torch.equal(deq(b8, sb), b)
+        out = torch.full((M, N), float("nan"), device="cuda")
+        ops.gemm_last_path(reset=True)
+        ops.gemm_fp8(ops.EPI_F32, a8, sa, b8, sb, out, M=M, N=N, K=K)
+        assert ops.gemm_last_path(reset=True).path == "fp8_nt"
+        assert torch.equal(out.double(), a.double() @ b.double().t()), (K, rep)
+
+
 def test_gemm_fp8_accuracy_on_activation_like_data():
     """Stated accuracy of the recipe: against the UNQUANTISED product the relative Frobenius error of one
     [tokens, 1024] x [4096, 1024]^T projection stays below 4 % (e4m3 round-off 2^-4 per element, averaged over K), and
