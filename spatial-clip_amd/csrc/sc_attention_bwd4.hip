@@ -65,8 +65,8 @@ struct B4Next {
 // dQ / dK / dV stores -- may be in flight (it cannot see that the DMA fills other rows).  With the builtin every wave waited for
 // its refills, for its dQ stores' acknowledgement and, at the start of a head, for the K image it had just requested: 5-6 us
 // of a 27-us head (rocprof phase stamps + the waits in the ISA).  The asm reads are invisible to the compiler's wait pass, so
-// the waits are written by hand and NAME the registers they retire (sc_gemm8p.hip, tn_wait4).  LDS operations return in
-// order: `lgkmcnt(n)` with n = the number of younger LDS operations of this wave retires everything older.
+// the waits are written by hand and NAME the registers they retire (sc_gemm8p.hip, OpsTN16::wait_b / wait_a).  LDS operations
+// return in order: `lgkmcnt(n)` with n = the number of younger LDS operations of this wave retires everything older.
 struct TrF { u32x2 lo, hi; };
 // One address register per fragment column group, everything else in the instruction's 16-bit offset field (the builtin let the
 // compiler fold constant offsets; asm operands do not fold, and one address register per read spills this kernel).

@@ -19,23 +19,7 @@ constexpr int STAGE = 2 * TILE;                     // A + B
 constexpr int EPI_BYTES = 8 * 64 * SC_EPI_LD * 4;   // 139264
 constexpr int LDS_BYTES = EPI_BYTES > 2 * STAGE ? EPI_BYTES : 2 * STAGE;
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-SC_DEVICE void dma16(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
-}
-
-// ds_read_b64_tr_b16 through inline asm.  In front of the builtin form hipcc places `s_waitcnt vmcnt(0)` whenever an
-// LDS-DMA is in flight (it cannot see that the DMA fills the OTHER stage), which serialises the prefetch of K tile
-// i+1 with the fragment reads of tile i; plain ds_read_b128 (the NT path) does not get that wait.  The asm form is
-// invisible to the waitcnt pass, so the lgkmcnt waits it would have placed are written by hand (tr_wait).
-template <int OFF>
-SC_DEVICE u32x2 tr16_asm(unsigned lds_addr) {
-    u32x2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
-    return r;
-}
+// dma16, tr16_asm and tr_cat: sc_gemm_common.h.  The lgkmcnt waits of the asm reads (tr16_asm), written by hand:
 template <int CNT>
 SC_DEVICE void tr_wait(u32x2& a, u32x2& b) {
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(CNT) : "memory");
@@ -45,11 +29,6 @@ SC_DEVICE void tr_wait_b(u32x2 (&lo)[4], u32x2 (&hi)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%8)"
                  : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3])
                  : "n"(CNT) : "memory");
-}
-SC_DEVICE bf16x8 tr_cat(u32x2 lo, u32x2 hi) {
-    union { u32x4 u; bf16x8 b; } c;
-    c.u = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-    return c.b;
 }
 
 // Issue the LDS-DMA of one K tile (A and B) : 8 wave-instructions per wave.

@@ -1,4 +1,5 @@
-// 256x256x64 bf16 MFMA GEMM with a phase-interleaved ("ping-pong") main loop, gfx950.  NT layout only.
+// 256x256x64 MFMA GEMMs with a phase-interleaved ("ping-pong") main loop, gfx950: bf16 and e4m3 operands, NT and TN layouts.
+// The schedule is described for the bf16 NT kernel; the others differ in their operand policy only.
 //
 //   8 waves (2 x 4), each wave a 128x64 output tile (128 accumulator VGPRs) cut into four 64x32 quadrants.
 //   A K tile (64 deep) is four phases, one quadrant each: {fragment ds_reads + 2 LDS-DMA of a later half-tile ->
@@ -20,6 +21,11 @@
 //   Epilogue: bf16 outputs without an extra input tile take a bf16 LDS strip (epilogue_bf16_lds); the others the
 //   fp32 LDS staging shared with sc_gemm256.hip (sc_gemm_common.h).
 //
+//   Layout of this file: the operand policies (bf16 NT, e4m3 NT, bf16 TN, e4m3 TN: fragment types, reads, waits, MFMAs,
+//   staging), then the schedules written once over them (phase / ktile, hphase, pphase), then the six kernels
+//   (gemm8p_kernel, gemm8pp_kernel, gemm8p_tn_kernel, gemm8p_tn_group_kernel, gemm8p_tn_f8_kernel, gemm8p_f8_kernel), then
+//   the host side (launch_lds, epi_dispatch, splitk_plan and the entry points).
+//
 //   Tail split (non-persistent kernel, splitk == 1): the tiles of a launch's partial last round run as HALF TILES of 128 rows
 //   (half_tile below: two phases and three images per K tile, nine-slot ring -- the same two rules, derived there), one per
 //   CU, so the round costs a half tile's time.  Which launches: sc_debug_gemm_tail_rule / sc_tail_default at the launcher.
@@ -27,6 +33,7 @@
 #include <stdlib.h>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -35,13 +42,6 @@ constexpr int HALF = 128 * 64 * 2;                  // 16 KiB half-tile
 constexpr int RING = 8 * HALF;                      // 128 KiB
 constexpr int EPI_BYTES = 8 * 64 * SC_EPI_LD * 4;   // 139264 (LDS-staged epilogues)
 constexpr int LDS_BYTES = EPI_BYTES > RING ? EPI_BYTES : RING;
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-SC_DEVICE void dma16(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 // bf16 epilogue through a small wave-private LDS strip (4 KiB: 32 rows x 128 B), four passes per 128x64 wave tile.
 // Why: a store instruction that writes whole 128-B lines (8 rows x 128 B) retires 3.7x faster than the 16 rows x 64 B
@@ -154,78 +154,388 @@ SC_DEVICE void epilogue_bf16_lds(f32x4 (&acc)[NI][4], const GemmArgs& g, char* s
 // ring slot of half-tile q (0: A half 0, 1: B half 0, 2: B half 1, 3: A half 1) of the K tile with parity D
 constexpr int slot(int D, int q) { return D * 4 * HALF + q * HALF; }
 
+// the barrier the two wave groups meet at, fenced so that the compiler moves nothing across it
+SC_DEVICE void fenced_barrier() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// =====================================================================================================================
+// Operand policies: what really differs between the kernels of this file.  A policy names its fragment types and supplies
+//   read_a<Q> / read_b<Q>   the fragment reads from half-tile Q of the K tile image set at `par`,
+//   wait_a / wait_b         the hand-written lgkmcnt wait that names the registers it retires (empty where the compiler
+//                           sees the reads),
+//   mfma<MI, NJ, NEWA>      the MFMAs of quadrant (MI, NJ); NEWA = the A fragments are used for the first time, which is when
+//                           the TN policies take their fused column sum (their extra arguments do_cs, wc, cs: the `hook`
+//                           pack of the schedules, empty for NT),
+//   stage(S, q, ts, dst)    the two LDS-DMA pieces of half-tile q of K tile ts, with its source addressing.
+// The schedules below (phase / hphase / pphase) are written once over these pieces.
 struct Stager {
     const bf16* src[4][2];      // [q][p] : this lane's source of the two 1-KiB pieces it copies per half-tile
     int nt;
     int wave;
 };
 
-// One phase of K tile `t` (ring parity D):  PH = 1..4  <->  quadrant (0,0) (0,1) (1,1) (1,0).
-template <int D, int PH>
-SC_DEVICE void phase(char* smem, const Stager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
-                     bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[8][4]) {
-    // ---- load section: fragments of this quadrant that are not in registers yet ----
-    if (PH == 1) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b0[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + slot(D, 1) + b_off[kk] + jj * 2048);
+struct OpsNT {                  // NT layout: what the bf16 and the e4m3 kernel share (per-lane source pointers, visible reads)
+    typedef Stager Src;
+    typedef const char* Ring;
+    typedef int Off;
+    static constexpr int NOA = 2, NOB = 2;
+    static SC_DEVICE Ring ring(char* smem) { return smem; }
+    // the two 1-KiB pieces of one half-tile, `eoff` elements along K behind the lane's sources
+    static SC_DEVICE void stage_pair(const bf16* s0, const bf16* s1, long long eoff, char* dst, int wave) {
+        dma16(s0 + eoff, dst + wave * 1024);
+        dma16(s1 + eoff, dst + (8 + wave) * 1024);
     }
-    if (PH == 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b1[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + slot(D, 2) + b_off[kk] + jj * 2048);
+    static SC_DEVICE void stage(const Stager& S, int q, int ts, char* dst) {
+        stage_pair(S.src[q][0], S.src[q][1], (size_t)ts * BK, dst, S.wave);
     }
-    if (PH == 1 || PH == 3) {
-        constexpr int sl = slot(D, PH == 1 ? 0 : 3);
+    template <class F>
+    static SC_DEVICE void wait_a(F&) {}
+    template <class F>
+    static SC_DEVICE void wait_b(F&) {}
+};
+
+struct OpsNT16 : OpsNT {        // bf16 NT
+    typedef bf16x8 Frag;
+    static constexpr int NA = 8, NB = 4;
+    template <int Q>
+    static SC_DEVICE void read_a(const char* par, const int (&a_off)[2], bf16x8 (&a)[8]) {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii)
-                a[kk * 4 + ii] = *reinterpret_cast<const bf16x8*>(smem + sl + a_off[kk] + ii * 2048);
+                a[kk * 4 + ii] = *reinterpret_cast<const bf16x8*>(par + Q * HALF + a_off[kk] + ii * 2048);
     }
+    template <int Q>
+    static SC_DEVICE void read_b(const char* par, const int (&b_off)[2], bf16x8 (&b)[4]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                b[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(par + Q * HALF + b_off[kk] + jj * 2048);
+    }
+    template <int MI, int NJ, bool NEWA, int NI>
+    static SC_DEVICE void mfma(const bf16x8 (&a)[8], const bf16x8 (&b)[4], f32x4 (&acc)[NI][4]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+                    acc[MI * 4 + ii][NJ * 2 + jj] = sc_mfma16(b[kk * 2 + jj], a[kk * 4 + ii], acc[MI * 4 + ii][NJ * 2 + jj]);
+    }
+};
+
+// FP8 (OCP e4m3) NT: the same tile, ring, phase schedule and epilogues on one-byte operands.  A half-tile row
+// is still 128 bytes, i.e. 128 k values instead of 64, so the staging stream, swizzle and waits are byte-for-byte the
+// bf16 kernel's; the caller passes K / 2, lda / 2, ldb / 2 ("bf16 elements") and the MFMA section issues ONE
+// v_mfma_scale_f32_16x16x128_f8f6f4 per fragment pair where the bf16 kernel issues two 16x16x32: half the MFMA count
+// for twice the k per tile = 2x the matrix rate.  Operand layout (probed with integer data, tools/micro/
+// mfma_fp8_layout.hip): lane (g = lane >> 4, r = lane & 15) supplies row r and the 32 consecutive k of bytes
+// [32 g, 32 g + 32) of the 128-byte row = the two 16-byte chunks 2g, 2g + 1; the block scales are E8M0 1.0 -- the real
+// scales are per-row floats applied to the accumulators before the epilogue:
+//     C[m][n] = a_scale[m] * b_scale[n] * sum_k A8[m][k] B8[n][k]   (+ bias, residual, GELU as in the bf16 kernel).
+// Block scales of the f8f6f4 MFMA.  Unit scales two ways: E8M0 127 (= 2^0) in the scale registers of the SCALED opcode
+// (v_mfma_scale_..., a 16-byte encoding that loads the scales in front of every MFMA), or the constant 0, for which the compiler
+// selects the UNSCALED opcode v_mfma_f32_16x16x128_f8f6f4 (8-byte encoding, no scale load; the scales are implicitly one).
+// -DSC_F8_SCALED_OPCODE keeps the first form (A/B; tests/test_gpu_fp8.py's exact-integer tests pin the arithmetic of either).
+#ifdef SC_F8_SCALED_OPCODE
+#define SC_F8_UNIT_SCALE 0x7F7F7F7F
+#else
+#define SC_F8_UNIT_SCALE 0
+#endif
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+SC_DEVICE f32x4 mfma_f8(i32x8 b, i32x8 a, f32x4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, c, 0, 0, 0, SC_F8_UNIT_SCALE, 0, SC_F8_UNIT_SCALE);
+}
+struct Frag8 {
+    union { i32x8 v; u32x4 h[2]; };
+};
+
+struct OpsNT8 : OpsNT {         // e4m3 NT
+    typedef Frag8 Frag;
+    static constexpr int NA = 4, NB = 2;
+    template <int Q>
+    static SC_DEVICE void read_a(const char* par, const int (&a_off)[2], Frag8 (&a)[4]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii)
+                a[ii].h[kk] = *reinterpret_cast<const u32x4*>(par + Q * HALF + a_off[kk] + ii * 2048);
+    }
+    template <int Q>
+    static SC_DEVICE void read_b(const char* par, const int (&b_off)[2], Frag8 (&b)[2]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                b[jj].h[kk] = *reinterpret_cast<const u32x4*>(par + Q * HALF + b_off[kk] + jj * 2048);
+    }
+    template <int MI, int NJ, bool NEWA, int NI>
+    static SC_DEVICE void mfma(const Frag8 (&a)[4], const Frag8 (&b)[2], f32x4 (&acc)[NI][4]) {
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+                acc[MI * 4 + ii][NJ * 2 + jj] = mfma_f8(b[jj].v, a[ii].v, acc[MI * 4 + ii][NJ * 2 + jj]);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// TN layout (weight gradients): C[m,n] = sum_k At[k,m] Bt[k,n], both operands k-major in global memory.
+//   Half-tile image = [64 k][128 columns] bf16 (256-B rows); A half i = tile columns [128 i, 128 i + 128), of which
+//   M-wave wr owns [64 wr, 64 wr + 64); B half j likewise with N-wave wc owning [32 wc, 32 wc + 32) -- so a wave's
+//   128x64 output is rows {128 i + 64 wr + ..} x columns {128 j + 32 wc + ..} (2 x 2 blocks of 64 x 32), and every
+//   DMA row is one contiguous 256-B run of the source.  Fragments come out of LDS through ds_read_b64_tr_b16 (inline
+//   asm + hand-placed lgkmcnt: see sc_gemm_common.h), 32-B chunk ^= (k & 3) | ((k >> 3) & 1) << 2 keeps the 8 rows a
+//   32-lane half touches on distinct banks.  Phase / ring schedule identical to the NT kernel.
+struct StagerTN {
+    // wave-uniform base (SGPRs) + 32-bit per-lane byte offset: the DMA takes the scalar-base addressing form (no address VALU, 4
+    // VGPRs instead of 16; with 64-bit pointers the e4m3 kernel spilled them and reloaded one before every DMA); piece 1 of a
+    // half-tile is half a K tile of source rows behind piece 0 = a scalar addend (step / 2)
+    const char* base[4];
+    unsigned off[4];
+    long long step[4];          // BYTES per K tile (bf16: 64 source rows, e4m3: 128) for each half-tile kind
+    int nt;
+    int wave;
+};
+struct OpsTN {                  // TN layout: what the bf16 and the e4m3 kernel share (scalar-base sources, asm reads)
+    typedef StagerTN Src;
+    typedef unsigned Ring;      // LDS byte address: the operand of the asm reads
+    typedef unsigned Off;
+    static constexpr int NOA = 4, NOB = 2;
+    static SC_DEVICE Ring ring(char* smem) { return (unsigned)(uintptr_t)(lptr_t)smem; }
+    // PIN = false: the prologue's DMAs, which run once and never needed the pin
+    template <bool PIN = true>
+    static SC_DEVICE void stage(const StagerTN& S, int q, int ts, char* dst) {
+        const char* kb = S.base[q] + ts * S.step[q];
+        unsigned o0 = S.off[q];
+        if (PIN) asm volatile("" : "+v"(o0));      // keep (scalar base + 32-bit offset): no hoisted 64-bit sums, which cost 2 VGPRs each
+        dma16(kb + o0, dst + S.wave * 1024);
+        dma16(kb + (S.step[q] >> 1) + o0, dst + (8 + S.wave) * 1024);
+    }
+};
+
+struct FragTN {                 // one operand fragment set: [kk][f] as two 64-bit halves
+    u32x2 lo, hi;
+};
+struct OpsTN16 : OpsTN {        // bf16 TN
+    typedef FragTN Frag;
+    static constexpr int NA = 8, NB = 4;
+    template <int NF>
+    static SC_DEVICE void read(unsigned base, const unsigned (&off)[NF], FragTN (&f)[2 * NF]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int x = 0; x < NF; ++x) {
+                if (kk == 0) {
+                    f[x].lo = tr16_asm<0>(base + off[x]);
+                    f[x].hi = tr16_asm<1024>(base + off[x]);
+                } else {
+                    f[NF + x].lo = tr16_asm<8192>(base + off[x]);
+                    f[NF + x].hi = tr16_asm<8192 + 1024>(base + off[x]);
+                }
+            }
+    }
+    template <int Q>
+    static SC_DEVICE void read_a(unsigned par, const unsigned (&a_off)[4], FragTN (&a)[8]) { read<4>(par + Q * HALF, a_off, a); }
+    template <int Q>
+    static SC_DEVICE void read_b(unsigned par, const unsigned (&b_off)[2], FragTN (&b)[4]) { read<2>(par + Q * HALF, b_off, b); }
+    // The asm reads above are invisible to hipcc's waitcnt pass, so the wait is written by hand -- and it must NAME the
+    // registers it retires ("+v"): a clobber-only `s_waitcnt` orders memory, not registers, and the compiler may copy or
+    // consume an asm-loaded register in front of it (seen in the attention kernels).  Same pattern as
+    // tr_wait / tr_wait_b in sc_gemm256.hip.
+    static SC_DEVICE void wait_b(FragTN (&f)[4]) {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo),
+                       "+v"(f[3].hi)
+                     :: "memory");
+    }
+    static SC_DEVICE void wait_a(FragTN (&f)[8]) {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo),
+                       "+v"(f[3].hi), "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi), "+v"(f[6].lo), "+v"(f[6].hi),
+                       "+v"(f[7].lo), "+v"(f[7].hi)
+                     :: "memory");
+    }
+    template <int MI, int NJ, bool NEWA>
+    static SC_DEVICE void mfma(const FragTN (&a)[8], const FragTN (&b)[4], f32x4 (&acc)[8][4], bool do_cs, int wc, float* cs) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) {
+                const bf16x8 af = tr_cat(a[kk * 4 + ii].lo, a[kk * 4 + ii].hi);
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    const FragTN& bf = b[kk * 2 + jj];
+                    acc[MI * 4 + ii][NJ * 2 + jj] = sc_mfma16(tr_cat(bf.lo, bf.hi), af, acc[MI * 4 + ii][NJ * 2 + jj]);
+                }
+                // fused bias gradient: column sums of At over this K tile, one 16-column fragment per wave (ii == wc),
+                // taken from the A fragments when they are first used (PH 1: half 0, PH 3: half 1); the VALU adds sit
+                // between the MFMAs so they issue in the matrix pipe's shadow
+                if (NEWA && do_cs && ii == wc) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) cs[MI] += (float)af[e];
+                }
+            }
+    }
+};
+
+// FP8 (OCP e4m3) TN: weight gradients dW[m, n] = sum_k A8[k, m] B8[k, n] with both operands token-major bytes
+// quantised with ONE scale per tensor (the reduction runs over the tokens, so a per-token scale cannot be pulled out of it).
+//   K tile = 128 tokens; half-tile image = [128 k][128 columns] bytes (16 KiB, 128-B rows): the ring, the DMA piece count and the
+//   phase schedule are byte-for-byte those of the bf16 TN kernel above, with twice the k per tile.
+//   Fragments: the MFMA (v_mfma_scale_f32_16x16x128_f8f6f4) wants, in lane (g = lane >> 4, r = lane & 15), the 32 consecutive k
+//   [32 g, 32 g + 32) of output row r, one per byte.  ds_read_b64_tr_b8 (layout probed with tools/micro/tr_b8_layout.hip: lane
+//   2 q + p of a 16-lane group supplies the address of (row q, byte columns 8 p .. 8 p + 7); lane i receives column i of rows
+//   0 .. 7) delivers 8 of them: four reads per fragment at k offsets 0, 8, 16, 24 (+1024 B each in the image).
+//   Swizzle: 16-byte chunk ^= ((k >> 1) & 3) | ((k >> 5) & 1) << 2 -- the four same-parity rows of an 8-row block and the two
+//   row blocks a 32-lane half reads land on eight different 16-byte bank windows; the per-lane swizzle term does not depend on
+//   which of the four reads it is, so they are immediate offsets off one address.
+//   C = a_scale_inv * b_scale_inv * sum (fp32 slabs as above); the fused bias gradient sums the e4m3 A fragments (x a_scale_inv).
+struct FragT8 {
+    union {
+        i32x8 v;                // the MFMA operand: 8 consecutive registers
+        u32x2 q[4];             // k blocks 0..7, 8..15, 16..23, 24..31 of this lane's group (one transposed read each)
+    };
+};
+template <int OFF>
+SC_DEVICE u32x2 tr8_asm(unsigned lds_addr) {
+    u32x2 r;
+    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
+    return r;
+}
+struct OpsTN8 : OpsTN {         // e4m3 TN
+    typedef FragT8 Frag;
+    static constexpr int NA = 4, NB = 2;
+    // Q = half-tile index inside one ring parity: its byte offset (<= 48 KiB) rides in the instruction's 16-bit offset field, so a
+    // fragment needs ONE address register per ring parity instead of one per ring slot (with the slot folded into the address the
+    // compiler keeps ~24 hoisted address registers and spills); the ring parity base is part of the (hoisted) address
+    template <int Q>
+    static SC_DEVICE void read(unsigned addr, FragT8& f) {
+        f.q[0] = tr8_asm<Q * HALF>(addr);
+        f.q[1] = tr8_asm<Q * HALF + 1024>(addr);
+        f.q[2] = tr8_asm<Q * HALF + 2048>(addr);
+        f.q[3] = tr8_asm<Q * HALF + 3072>(addr);
+    }
+    template <int Q>
+    static SC_DEVICE void read_a(unsigned par, const unsigned (&a_off)[4], FragT8 (&a)[4]) {
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) read<Q>(par + a_off[ii], a[ii]);
+    }
+    template <int Q>
+    static SC_DEVICE void read_b(unsigned par, const unsigned (&b_off)[2], FragT8 (&b)[2]) {
+        read<Q>(par + b_off[0], b[0]);
+        read<Q>(par + b_off[1], b[1]);
+    }
+    // retire every register the asm reads above wrote (see OpsTN16::wait_b)
+    static SC_DEVICE void wait_b(FragT8 (&f)[2]) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].v), "+v"(f[1].v)::"memory"); }
+    static SC_DEVICE void wait_a(FragT8 (&f)[4]) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].v), "+v"(f[1].v), "+v"(f[2].v), "+v"(f[3].v)::"memory");
+    }
+    static SC_DEVICE float sum(const FragT8& f) {       // sum of this lane's 32 e4m3 values
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                const int v = (int)f.q[j][w];
+                s += __builtin_amdgcn_cvt_f32_fp8(v, 0) + __builtin_amdgcn_cvt_f32_fp8(v, 1) + __builtin_amdgcn_cvt_f32_fp8(v, 2) +
+                     __builtin_amdgcn_cvt_f32_fp8(v, 3);
+            }
+        return s;
+    }
+    template <int MI, int NJ, bool NEWA>
+    static SC_DEVICE void mfma(const FragT8 (&a)[4], const FragT8 (&b)[2], f32x4 (&acc)[8][4], bool do_cs, int wc, float* cs) {
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+            const i32x8 af = a[ii].v;
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) acc[MI * 4 + ii][NJ * 2 + jj] = mfma_f8(b[jj].v, af, acc[MI * 4 + ii][NJ * 2 + jj]);
+            if (NEWA && do_cs && ii == wc) cs[MI] += sum(a[ii]);      // fused bias gradient, as in the bf16 kernel
+        }
+    }
+};
+
+// =====================================================================================================================
+// Schedules: phase / ktile (standard 8-slot ring, every operand policy), hphase (half tile: three images, nine slots) and
+// pphase (persistent: staging cursor across tiles, post-epilogue waits) share the load section, the MFMA section and the
+// fenced barrier below.
+// What is shared is straight-line code over register arrays, which inlines to the text it replaced.  The tile frame around
+// the K loop -- per-lane sources and offsets, accumulator zeroing, prologue, ring loop, re-align, epilogue choice -- stays
+// written out in each kernel on purpose: the compiler simplifies a helper on its own before it inlines it, without what the
+// kernel knows (lane < 64, m0 a multiple of 256, ...), and every attempt to share one of those pieces (also the wait and
+// barrier tail of the prologue alone) changed the instruction stream of the kernels it touched (profiles/gemm8p_fold_isa.txt).
+//
+// The LDS offsets a wave reads its fragments at (inside a half-tile image), and its fragment registers:
+template <class Ops>
+struct FragOffs {
+    typename Ops::Off a[Ops::NOA], b[Ops::NOB];
+};
+template <class Ops>
+struct Frags {
+    typename Ops::Frag a[Ops::NA], b0[Ops::NB], b1[Ops::NB];
+};
+
+// Load section of phase PH (1..4  <->  quadrant (0,0) (0,1) (1,1) (1,0)): the fragments of this quadrant that are not in
+// registers yet, from the K tile whose images start at `par`.
+template <class Ops, int PH>
+SC_DEVICE void load_section(typename Ops::Ring par, const FragOffs<Ops>& O, Frags<Ops>& F) {
+    if (PH == 1) Ops::template read_b<1>(par, O.b, F.b0);
+    if (PH == 2) Ops::template read_b<2>(par, O.b, F.b1);
+    if (PH == 1) Ops::template read_a<0>(par, O.a, F.a);
+    if (PH == 3) Ops::template read_a<3>(par, O.a, F.a);
+}
+
+// MFMA section of quadrant (MI, NJ), and the barrier that ends the phase
+template <class Ops, int MI, int NJ, bool NEWA, int NI, class... Hook>
+SC_DEVICE void mfma_section(Frags<Ops>& F, f32x4 (&acc)[NI][4], Hook... hook) {
+    __builtin_amdgcn_s_setprio(1);
+    Ops::template mfma<MI, NJ, NEWA>(F.a, NJ ? F.b1 : F.b0, acc, hook...);
+    __builtin_amdgcn_s_setprio(0);
+    fenced_barrier();
+}
+
+// One phase of K tile `t` (ring parity D) on the standard 8-slot schedule.
+template <class Ops, int D, int PH, class... Hook>
+SC_DEVICE void phase(char* smem, const typename Ops::Src& S, int t, const FragOffs<Ops>& O, Frags<Ops>& F, f32x4 (&acc)[8][4], Hook... hook) {
+    load_section<Ops, PH>(Ops::ring(smem) + D * 4 * HALF, O, F);
     // ---- stage the half-tile six positions ahead (consumption order A0 B0 B1 A1) ----
     constexpr int q = (PH + 1) & 3;
     constexpr int DS = PH <= 2 ? (D ^ 1) : D;
     const int ts = t + (PH <= 2 ? 1 : 2);
     if (ts < S.nt) {
-        dma16(S.src[q][0] + (size_t)ts * BK, smem + slot(DS, q) + S.wave * 1024);
-        dma16(S.src[q][1] + (size_t)ts * BK, smem + slot(DS, q) + (8 + S.wave) * 1024);
+        Ops::stage(S, q, ts, smem + slot(DS, q));
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // retires the half-tile read in the NEXT phase
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // ring is draining: fewer than four in flight
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
+    // every fragment register this phase's asm reads wrote is tied to the wait that retires it
+    if (PH == 1) { Ops::wait_b(F.b0); Ops::wait_a(F.a); }
+    if (PH == 2) Ops::wait_b(F.b1);
+    if (PH == 3) Ops::wait_a(F.a);
     __builtin_amdgcn_sched_barrier(0);
-    // ---- MFMA section ----
-    constexpr int mi = PH >= 3 ? 1 : 0;
-    constexpr int nj = (PH == 2 || PH == 3) ? 1 : 0;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                acc[mi * 4 + ii][nj * 2 + jj] =
-                    sc_mfma16(nj ? b1[kk * 2 + jj] : b0[kk * 2 + jj], a[kk * 4 + ii], acc[mi * 4 + ii][nj * 2 + jj]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    mfma_section<Ops, (PH >= 3), (PH == 2 || PH == 3), (PH == 1 || PH == 3)>(F, acc, hook...);
 }
 
-template <int D>
-SC_DEVICE void ktile(char* smem, const Stager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
-                     bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[8][4]) {
-    phase<D, 1>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase<D, 2>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase<D, 3>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase<D, 4>(smem, S, t, a_off, b_off, a, b0, b1, acc);
+template <class Ops, int D, class... Hook>
+SC_DEVICE void ktile(char* smem, const typename Ops::Src& S, int t, const FragOffs<Ops>& O, Frags<Ops>& F, f32x4 (&acc)[8][4], Hook... hook) {
+    phase<Ops, D, 1>(smem, S, t, O, F, acc, hook...);
+    phase<Ops, D, 2>(smem, S, t, O, F, acc, hook...);
+    phase<Ops, D, 3>(smem, S, t, O, F, acc, hook...);
+    phase<Ops, D, 4>(smem, S, t, O, F, acc, hook...);
+}
+
+// (z, tm, tn) of tile index idx = (z * ntm + tm) * ntn + tn
+SC_DEVICE void tile_decode(int idx, const GemmArgs& g, int& z, int& tm, int& tn) {
+    tn = idx % g.ntn;
+    idx /= g.ntn;
+    tm = idx % g.ntm;
+    z = idx / g.ntm;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -253,73 +563,25 @@ SC_DEVICE void ktile(char* smem, const Stager& S, int t, const int (&a_off)[2], 
 constexpr int HRING = 9 * HALF;                     // 144 KiB
 constexpr int hslot(int D, int q) { return (D * 3 + q) * HALF; }      // q: 0 A0', 1 B0, 2 B1 of the K tile with t % 3 == D
 
-struct HStager {
-    const bf16* src[3][2];
-    int nt;
-    int wave;
-};
-
 template <int D, int PH>
-SC_DEVICE void hphase(char* smem, const HStager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
-                      bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[4][4]) {
-    if (PH == 1) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b0[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 1) + b_off[kk] + jj * 2048);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii)
-                a[kk * 4 + ii] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 0) + a_off[kk] + ii * 2048);
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b1[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(smem + hslot(D, 2) + b_off[kk] + jj * 2048);
-    }
+SC_DEVICE void hphase(char* smem, const Stager& S, int t, const FragOffs<OpsNT16>& O, Frags<OpsNT16>& F, f32x4 (&acc)[4][4]) {
+    load_section<OpsNT16, PH>(smem + hslot(D, 0), O, F);
     constexpr int DS = (D + 2) % 3;
     const int ts = t + 2;
     if (ts < S.nt) {
         if (PH == 1) {
-            dma16(S.src[0][0] + (size_t)ts * BK, smem + hslot(DS, 0) + S.wave * 1024);
-            dma16(S.src[0][1] + (size_t)ts * BK, smem + hslot(DS, 0) + (8 + S.wave) * 1024);
-            dma16(S.src[1][0] + (size_t)ts * BK, smem + hslot(DS, 1) + S.wave * 1024);
-            dma16(S.src[1][1] + (size_t)ts * BK, smem + hslot(DS, 1) + (8 + S.wave) * 1024);
+            OpsNT16::stage(S, 0, ts, smem + hslot(DS, 0));
+            OpsNT16::stage(S, 1, ts, smem + hslot(DS, 1));
             asm volatile("s_waitcnt vmcnt(10)" ::: "memory");     // retires B1(t), read in the NEXT phase
         } else {
-            dma16(S.src[2][0] + (size_t)ts * BK, smem + hslot(DS, 2) + S.wave * 1024);
-            dma16(S.src[2][1] + (size_t)ts * BK, smem + hslot(DS, 2) + (8 + S.wave) * 1024);
+            OpsNT16::stage(S, 2, ts, smem + hslot(DS, 2));
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // retires A0', B0 of K tile t + 1
         }
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int nj = PH - 1;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                acc[ii][nj * 2 + jj] = sc_mfma16(nj ? b1[kk * 2 + jj] : b0[kk * 2 + jj], a[kk * 4 + ii], acc[ii][nj * 2 + jj]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-SC_DEVICE void hktile(char* smem, const HStager& S, int t, const int (&a_off)[2], const int (&b_off)[2], bf16x8 (&a)[8],
-                      bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[4][4]) {
-    hphase<D, 1>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    hphase<D, 2>(smem, S, t, a_off, b_off, a, b0, b1, acc);
+    fenced_barrier();
+    mfma_section<OpsNT16, 0, PH - 1, false>(F, acc);
 }
 
 // rows [mh, mh + 128) x columns [n0, n0 + 256) of the product (splitk == 1); the caller has checked mh < g.M
@@ -331,13 +593,13 @@ SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
     const int wr = wave >> 2, wc = wave & 3;
     const int li = lane & 15, lg = lane >> 4;
 
-    HStager S;
+    Stager S;
     S.nt = g.K / BK;
     S.wave = wave;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int r = (p * 8 + wave) * 8 + (lane >> 3);          // row of the image, 128 B per row
-        const int lc = (lane & 7) ^ ((r >> 1) & 7);
+        const int r = (p * 8 + wave) * 8 + (lane >> 3);          // row of the half-tile image, 128 B per row
+        const int lc = (lane & 7) ^ ((r >> 1) & 7);              // logical 16-byte chunk stored at physical lane&7
         const int ga = min(mh + r, g.M - 1);
         S.src[0][p] = g.A + (size_t)ga * g.lda + lc * 8;
 #pragma unroll
@@ -346,12 +608,12 @@ SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
             S.src[1 + h][p] = g.B + (size_t)gb * g.ldb + lc * 8;
         }
     }
-    int a_off[2], b_off[2];
+    FragOffs<OpsNT16> O;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const int coff = ((kk * 4 + lg) ^ ((li >> 1) & 7)) << 4;
-        a_off[kk] = (wr * 64 + li) * 128 + coff;
-        b_off[kk] = (wc * 32 + li) * 128 + coff;
+        O.a[kk] = (wr * 64 + li) * 128 + coff;
+        O.b[kk] = (wc * 32 + li) * 128 + coff;
     }
     f32x4 acc[4][4];
 #pragma unroll
@@ -363,10 +625,7 @@ SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ts = s / 3, q = s % 3;
-        if (ts < S.nt) {
-            dma16(S.src[q][0] + (size_t)ts * BK, smem + hslot(ts, q) + wave * 1024);
-            dma16(S.src[q][1] + (size_t)ts * BK, smem + hslot(ts, q) + (8 + wave) * 1024);
-        }
+        if (ts < S.nt) OpsNT16::stage(S, q, ts, smem + hslot(ts, q));
     }
     if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -375,19 +634,20 @@ SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
     if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    bf16x8 a[8], b0[4], b1[4];
+    Frags<OpsNT16> F;
     for (int kt = 0; kt < S.nt; kt += 3) {
-        hktile<0>(smem, S, kt, a_off, b_off, a, b0, b1, acc);
-        if (kt + 1 < S.nt) hktile<1>(smem, S, kt + 1, a_off, b_off, a, b0, b1, acc);
-        if (kt + 2 < S.nt) hktile<2>(smem, S, kt + 2, a_off, b_off, a, b0, b1, acc);
+        hphase<0, 1>(smem, S, kt, O, F, acc);
+        hphase<0, 2>(smem, S, kt, O, F, acc);
+        if (kt + 1 < S.nt) { hphase<1, 1>(smem, S, kt + 1, O, F, acc); hphase<1, 2>(smem, S, kt + 1, O, F, acc); }
+        if (kt + 2 < S.nt) { hphase<2, 1>(smem, S, kt + 2, O, F, acc); hphase<2, 2>(smem, S, kt + 2, O, F, acc); }
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-
     // the full tile's epilogues on a 64-row wave tile: two strip passes / one fp32 staging block
     const int row0 = mh + wr * 64, col0 = n0 + wc * 64;
     if (EPI == SC_EPI_GELU_GRAD_PAIR && g.gelu_lut != nullptr) {
+        // the table moves into the dead operand ring (behind the eight 4-KiB strips) while the first strip pass is packed
         unsigned* lut = reinterpret_cast<unsigned*>(smem + 8 * 4096);
         for (int c = t; c < SC_GELU_LUT_N / 4; c += 512)
             reinterpret_cast<u32x4*>(lut)[c] = reinterpret_cast<const u32x4*>(g.gelu_lut)[c];
@@ -433,10 +693,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
         sc_tile_colgroup(idx, g, tm, tn);
         z = 0;
     } else {
-        tn = idx % g.ntn;
-        idx /= g.ntn;
-        tm = idx % g.ntm;
-        z = idx / g.ntm;
+        tile_decode(idx, g, z, tm, tn);
     }
     if (hh >= 0) {                                               // workgroup-uniform: every wave takes the same path
         const int mh = tm * BM + hh * 128;
@@ -468,12 +725,12 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
             S.src[h ? 2 : 1][p] = g.B + (size_t)gb * g.ldb + kbeg + lc * 8;
         }
     }
-    int a_off[2], b_off[2];
+    FragOffs<OpsNT16> O;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const int coff = ((kk * 4 + lg) ^ ((li >> 1) & 7)) << 4;
-        a_off[kk] = (wr * 64 + li) * 128 + coff;
-        b_off[kk] = (wc * 32 + li) * 128 + coff;
+        O.a[kk] = (wr * 64 + li) * 128 + coff;
+        O.b[kk] = (wc * 32 + li) * 128 + coff;
     }
 
     f32x4 acc[8][4];
@@ -486,10 +743,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ts = s >> 2, q = s & 3;
-        if (ts < S.nt) {
-            dma16(S.src[q][0] + (size_t)ts * BK, smem + slot(ts & 1, q) + wave * 1024);
-            dma16(S.src[q][1] + (size_t)ts * BK, smem + slot(ts & 1, q) + (8 + wave) * 1024);
-        }
+        if (ts < S.nt) OpsNT16::stage(S, q, ts, smem + slot(ts & 1, q));
     }
     if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -498,10 +752,10 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
     if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    bf16x8 a[8], b0[4], b1[4];
+    Frags<OpsNT16> F;
     for (int kt = 0; kt < S.nt; kt += 2) {
-        ktile<0>(smem, S, kt, a_off, b_off, a, b0, b1, acc);
-        if (kt + 1 < S.nt) ktile<1>(smem, S, kt + 1, a_off, b_off, a, b0, b1, acc);
+        ktile<OpsNT16, 0>(smem, S, kt, O, F, acc);
+        if (kt + 1 < S.nt) ktile<OpsNT16, 1>(smem, S, kt + 1, O, F, acc);
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -550,22 +804,6 @@ __global__ void sc_gelu_lut_fill_kernel(unsigned* lut, int act) {
     gq.b = (bf16)gv;
     lut[i] = ((unsigned)gq.s << 16) | (unsigned)h.s;
 }
-
-template <int EPI>
-int launch(const GemmArgs& g, int nblocks, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES > HRING ? LDS_BYTES : HRING);
-        attr_done = true;
-    }
-    // a launch with half tiles needs their nine-slot ring
-    const int lds = (g.tail_first > 0 && HRING > LDS_BYTES) ? HRING : LDS_BYTES;
-    gemm8p_kernel<EPI><<<nblocks, 512, lds, st>>>(g);
-    SC_LAUNCH_CHECK();
-    return 1;
-}
-
 
 // =====================================================================================================================
 // Persistent NT variant: one workgroup per CU walks a list of output tiles (tile = first + r * gridDim).  The staging
@@ -616,38 +854,15 @@ SC_DEVICE void pstage_advance(PStager& S, const GemmArgs& g, int lane) {
 
 // One phase; `doff` = byte offset of the ring half (parity) that holds the K tile being computed.
 template <int PH, int ESTORES>
-SC_DEVICE void pphase(char* smem, int doff, PStager& S, const GemmArgs& g, int lane, int pw, const int (&a_off)[2],
-                      const int (&b_off)[2], bf16x8 (&a)[8], bf16x8 (&b0)[4], bf16x8 (&b1)[4], f32x4 (&acc)[8][4]) {
-    const char* cur = smem + doff;
-    if (PH == 1) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b0[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(cur + 1 * HALF + b_off[kk] + jj * 2048);
-    }
-    if (PH == 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b1[kk * 2 + jj] = *reinterpret_cast<const bf16x8*>(cur + 2 * HALF + b_off[kk] + jj * 2048);
-    }
-    if (PH == 1 || PH == 3) {
-        constexpr int sl = (PH == 1 ? 0 : 3) * HALF;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii)
-                a[kk * 4 + ii] = *reinterpret_cast<const bf16x8*>(cur + sl + a_off[kk] + ii * 2048);
-    }
+SC_DEVICE void pphase(char* smem, int doff, PStager& S, const GemmArgs& g, int lane, int pw, const FragOffs<OpsNT16>& O,
+                      Frags<OpsNT16>& F, f32x4 (&acc)[8][4]) {
+    load_section<OpsNT16, PH>(smem + doff, O, F);
     // staging: the K tile under the cursor is (compute K tile + 1) in phases 1-2 and (+ 2) in phases 3-4
     constexpr int q = (PH + 1) & 3;
     char* dst = smem + (PH <= 2 ? (doff ^ (4 * HALF)) : doff) + q * HALF;
     if (PH == 3) pstage_advance(S, g, lane);
     if (S.stile < S.total) {
-        dma16(S.src[q][0] + S.koff, dst + S.wave * 1024);
-        dma16(S.src[q][1] + S.koff, dst + (8 + S.wave) * 1024);
+        OpsNT16::stage_pair(S.src[q][0], S.src[q][1], S.koff, dst, S.wave);
         if (PH <= 3 && pw == PW_POSTEPI) {
             constexpr int N = 8 + ESTORES > 63 ? 63 : 8 + ESTORES;
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -659,24 +874,8 @@ SC_DEVICE void pphase(char* smem, int doff, PStager& S, const GemmArgs& g, int l
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int mi = PH >= 3 ? 1 : 0;
-    constexpr int nj = (PH == 2 || PH == 3) ? 1 : 0;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                acc[mi * 4 + ii][nj * 2 + jj] =
-                    sc_mfma16(nj ? b1[kk * 2 + jj] : b0[kk * 2 + jj], a[kk * 4 + ii], acc[mi * 4 + ii][nj * 2 + jj]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    fenced_barrier();
+    mfma_section<OpsNT16, (PH >= 3), (PH == 2 || PH == 3), false>(F, acc);
 }
 
 template <int EPI>
@@ -701,42 +900,43 @@ __global__ __launch_bounds__(512, 2) void gemm8pp_kernel(const GemmArgs g, int t
     pstage_set_tile(S, g, lane);
     int ctile = S.stile;                                         // tile being computed
 
-    int a_off[2], b_off[2];
+    FragOffs<OpsNT16> O;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const int coff = ((kk * 4 + lg) ^ ((li >> 1) & 7)) << 4;
-        a_off[kk] = (wr * 64 + li) * 128 + coff;
-        b_off[kk] = (wc * 32 + li) * 128 + coff;
+        O.a[kk] = (wr * 64 + li) * 128 + coff;
+        O.b[kk] = (wc * 32 + li) * 128 + coff;
     }
+
     f32x4 acc[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // prologue: K tile 0 (four half-tiles) and A0, B0 of K tile 1 (the launcher guarantees nt >= 3)
+    // prologue: K tile 0 (four half-tiles) and A0, B0 of K tile 1.  The launcher guarantees nt >= 3, so every image exists:
+    // the constant stands for that, and the cursor moves to K tile 1 in front of its first image
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int q = s & 3;
         if (s == 4) pstage_advance(S, g, lane);
-        dma16(S.src[q][0] + S.koff, smem + slot(s >> 2, q) + wave * 1024);
-        dma16(S.src[q][1] + S.koff, smem + slot(s >> 2, q) + (8 + wave) * 1024);
+        OpsNT16::stage_pair(S.src[q][0], S.src[q][1], S.koff, smem + slot(s >> 2, q), wave);
     }
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    bf16x8 a[8], b0[4], b1[4];
+    Frags<OpsNT16> F;
     int k = 0;                                                   // K tile inside the tile being computed
     int pw = PW_STEADY;
     int doff = 0;                                                // ring half of the K tile being computed
     while (ctile < total_tiles) {
-        pphase<1, ESTORES>(smem, doff, S, g, lane, pw, a_off, b_off, a, b0, b1, acc);
-        pphase<2, ESTORES>(smem, doff, S, g, lane, pw, a_off, b_off, a, b0, b1, acc);
-        pphase<3, ESTORES>(smem, doff, S, g, lane, pw, a_off, b_off, a, b0, b1, acc);
-        pphase<4, ESTORES>(smem, doff, S, g, lane, pw, a_off, b_off, a, b0, b1, acc);
+        pphase<1, ESTORES>(smem, doff, S, g, lane, pw, O, F, acc);
+        pphase<2, ESTORES>(smem, doff, S, g, lane, pw, O, F, acc);
+        pphase<3, ESTORES>(smem, doff, S, g, lane, pw, O, F, acc);
+        pphase<4, ESTORES>(smem, doff, S, g, lane, pw, O, F, acc);
         doff ^= 4 * HALF;
         pw = PW_STEADY;
         if (++k == S.nt) {
@@ -759,152 +959,8 @@ __global__ __launch_bounds__(512, 2) void gemm8pp_kernel(const GemmArgs g, int t
     }
 }
 
-template <int EPI>
-int launch_persistent(const GemmArgs& g, int total_tiles, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8pp_kernel<EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, RING + 8 * 4096);
-        attr_done = true;
-    }
-    const int grid = total_tiles < 256 ? total_tiles : 256;
-    gemm8pp_kernel<EPI><<<grid, 512, RING + 8 * 4096, st>>>(g, total_tiles);
-    SC_LAUNCH_CHECK();
-    return 1;
-}
-
 // =====================================================================================================================
-// TN layout (weight gradients): C[m,n] = sum_k At[k,m] Bt[k,n], both operands k-major in global memory.
-//   Half-tile image = [64 k][128 columns] bf16 (256-B rows); A half i = tile columns [128 i, 128 i + 128), of which
-//   M-wave wr owns [64 wr, 64 wr + 64); B half j likewise with N-wave wc owning [32 wc, 32 wc + 32) -- so a wave's
-//   128x64 output is rows {128 i + 64 wr + ..} x columns {128 j + 32 wc + ..} (2 x 2 blocks of 64 x 32), and every
-//   DMA row is one contiguous 256-B run of the source.  Fragments come out of LDS through ds_read_b64_tr_b16 (inline
-//   asm + hand-placed lgkmcnt: see sc_gemm256.hip), 32-B chunk ^= (k & 3) | ((k >> 3) & 1) << 2 keeps the 8 rows a
-//   32-lane half touches on distinct banks.  Phase / ring schedule identical to the NT kernel above.
-template <int OFF>
-SC_DEVICE u32x2 tr16_asm(unsigned lds_addr) {
-    u32x2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
-    return r;
-}
-SC_DEVICE bf16x8 tr_cat(u32x2 lo, u32x2 hi) {
-    union { u32x4 u; bf16x8 b; } c;
-    c.u = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-    return c.b;
-}
-
-struct FragTN {                 // one operand fragment set: [kk][f] as two 64-bit halves
-    u32x2 lo, hi;
-};
-// The asm reads above are invisible to hipcc's waitcnt pass, so the wait is written by hand -- and it must NAME the
-// registers it retires ("+v"): a clobber-only `s_waitcnt` orders memory, not registers, and the compiler may copy or
-// consume an asm-loaded register in front of it (seen in the attention kernels).  Same pattern as
-// tr_wait / tr_wait_b in sc_gemm256.hip.
-SC_DEVICE void tn_wait4(FragTN (&f)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo),
-                   "+v"(f[3].hi)
-                 :: "memory");
-}
-SC_DEVICE void tn_wait8(FragTN (&f)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo),
-                   "+v"(f[3].hi), "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi), "+v"(f[6].lo), "+v"(f[6].hi),
-                   "+v"(f[7].lo), "+v"(f[7].hi)
-                 :: "memory");
-}
-
-template <int NF>
-SC_DEVICE void tn_read(unsigned base, const unsigned (&off)[NF], FragTN (&f)[2 * NF]) {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int x = 0; x < NF; ++x) {
-            if (kk == 0) {
-                f[x].lo = tr16_asm<0>(base + off[x]);
-                f[x].hi = tr16_asm<1024>(base + off[x]);
-            } else {
-                f[NF + x].lo = tr16_asm<8192>(base + off[x]);
-                f[NF + x].hi = tr16_asm<8192 + 1024>(base + off[x]);
-            }
-        }
-}
-
-struct StagerTN {
-    // wave-uniform base (SGPRs) + 32-bit per-lane byte offset: the DMA takes the scalar-base addressing form (no address VALU, 4
-    // VGPRs instead of 16); piece 1 of a half-tile is 32 k rows behind piece 0 = a scalar addend (round 4, from the e4m3 kernel)
-    const char* base[4];
-    unsigned off[4];
-    long long step[4];          // BYTES per K tile (64 source rows) for each half-tile kind
-    int nt;
-    int wave;
-};
-
-template <int D, int PH>
-SC_DEVICE void phase_tn(char* smem, unsigned lds0, const StagerTN& S, int t, const unsigned (&a_off)[4],
-                        const unsigned (&b_off)[2], FragTN (&a)[8], FragTN (&b0)[4], FragTN (&b1)[4], f32x4 (&acc)[8][4],
-                        bool do_cs, int wc, float (&cs)[2]) {
-    if (PH == 1) tn_read<2>(lds0 + slot(D, 1), b_off, b0);
-    if (PH == 2) tn_read<2>(lds0 + slot(D, 2), b_off, b1);
-    if (PH == 1) tn_read<4>(lds0 + slot(D, 0), a_off, a);
-    if (PH == 3) tn_read<4>(lds0 + slot(D, 3), a_off, a);
-    constexpr int q = (PH + 1) & 3;
-    constexpr int DS = PH <= 2 ? (D ^ 1) : D;
-    const int ts = t + (PH <= 2 ? 1 : 2);
-    if (ts < S.nt) {
-        const char* kb = S.base[q] + ts * S.step[q];
-        unsigned o0 = S.off[q];
-        asm volatile("" : "+v"(o0));                      // keep (scalar base + 32-bit offset): no hoisted 64-bit sums
-        dma16(kb + o0, smem + slot(DS, q) + S.wave * 1024);
-        dma16(kb + (S.step[q] >> 1) + o0, smem + slot(DS, q) + (8 + S.wave) * 1024);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // every fragment register this phase's reads wrote is tied to the wait that retires it
-    if (PH == 1) { tn_wait4(b0); tn_wait8(a); }
-    if (PH == 2) tn_wait4(b1);
-    if (PH == 3) tn_wait8(a);
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int mi = PH >= 3 ? 1 : 0;
-    constexpr int nj = (PH == 2 || PH == 3) ? 1 : 0;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            const bf16x8 af = tr_cat(a[kk * 4 + ii].lo, a[kk * 4 + ii].hi);
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const FragTN& bf = nj ? b1[kk * 2 + jj] : b0[kk * 2 + jj];
-                acc[mi * 4 + ii][nj * 2 + jj] = sc_mfma16(tr_cat(bf.lo, bf.hi), af, acc[mi * 4 + ii][nj * 2 + jj]);
-            }
-            // fused bias gradient: column sums of At over this K tile, one 16-column fragment per wave (ii == wc),
-            // taken from the A fragments when they are first used (PH 1: half 0, PH 3: half 1); the VALU adds sit
-            // between the MFMAs so they issue in the matrix pipe's shadow
-            if ((PH == 1 || PH == 3) && do_cs && ii == wc) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) cs[mi] += (float)af[e];
-            }
-        }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-SC_DEVICE void ktile_tn(char* smem, unsigned lds0, const StagerTN& S, int t, const unsigned (&a_off)[4],
-                        const unsigned (&b_off)[2], FragTN (&a)[8], FragTN (&b0)[4], FragTN (&b1)[4], f32x4 (&acc)[8][4],
-                        bool do_cs, int wc, float (&cs)[2]) {
-    phase_tn<D, 1>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_tn<D, 2>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_tn<D, 3>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_tn<D, 4>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-}
-
+// TN kernels (weight gradients; layouts: OpsTN16 / OpsTN8 above).
 // one 256x256 output tile (or split-K slab tile) of the TN product described by g; idx = (z * ntm + tm) * ntn + tn
 SC_DEVICE void tn_tile(const GemmArgs& g, int idx, char* smem) {
     const int t = threadIdx.x;
@@ -913,10 +969,8 @@ SC_DEVICE void tn_tile(const GemmArgs& g, int idx, char* smem) {
     const int wr = wave >> 2, wc = wave & 3;
     const int li = lane & 15, lg = lane >> 4;
 
-    const int tn = idx % g.ntn;
-    idx /= g.ntn;
-    const int tm = idx % g.ntm;
-    const int z = idx / g.ntm;
+    int z, tm, tn;
+    tile_decode(idx, g, z, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int kbeg = z * g.k_per_split;
     const int kend = min(g.K, kbeg + g.k_per_split);
@@ -940,16 +994,16 @@ SC_DEVICE void tn_tile(const GemmArgs& g, int idx, char* smem) {
     }
     S.base[0] = S.base[3] = reinterpret_cast<const char*>(g.A + (size_t)kbeg * g.lda);
     S.base[1] = S.base[2] = reinterpret_cast<const char*>(g.B + (size_t)kbeg * g.ldb);
-    const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem;
-    unsigned a_off[4], b_off[2];
+
+    FragOffs<OpsTN16> O;
     {
         const int q = li >> 2, p = li & 3;
         const int s = q | ((lg & 1) << 2);
         const int row = (lg * 8 + q) * 256 + p * 8;
 #pragma unroll
-        for (int ii = 0; ii < 4; ++ii) a_off[ii] = row + (((wr * 4 + ii) ^ s) << 5);
+        for (int ii = 0; ii < 4; ++ii) O.a[ii] = row + (((wr * 4 + ii) ^ s) << 5);
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) b_off[jj] = row + (((wc * 2 + jj) ^ s) << 5);
+        for (int jj = 0; jj < 2; ++jj) O.b[jj] = row + (((wc * 2 + jj) ^ s) << 5);
     }
 
     f32x4 acc[8][4];
@@ -960,31 +1014,27 @@ SC_DEVICE void tn_tile(const GemmArgs& g, int idx, char* smem) {
     const bool do_cs = g.colsum != nullptr && tn == 0;
     float cs[2] = {0.f, 0.f};
 
+    // prologue: the first six half-tiles (all of K tile 0, A0 and B0 of K tile 1)
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ts = s >> 2, q = s & 3;
-        if (ts < S.nt) {
-            const char* kb = S.base[q] + ts * S.step[q];
-            dma16(kb + S.off[q], smem + slot(ts & 1, q) + wave * 1024);
-            dma16(kb + (S.step[q] >> 1) + S.off[q], smem + slot(ts & 1, q) + (8 + wave) * 1024);
-        }
+        if (ts < S.nt) OpsTN16::stage<false>(S, q, ts, smem + slot(ts & 1, q));
     }
     if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    FragTN a[8], b0[4], b1[4];
+    Frags<OpsTN16> F;
     for (int kt = 0; kt < S.nt; kt += 2) {
-        ktile_tn<0>(smem, lds0, S, kt, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-        if (kt + 1 < S.nt) ktile_tn<1>(smem, lds0, S, kt + 1, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
+        ktile<OpsTN16, 0>(smem, S, kt, O, F, acc, do_cs, wc, cs);
+        if (kt + 1 < S.nt) ktile<OpsTN16, 1>(smem, S, kt + 1, O, F, acc, do_cs, wc, cs);
     }
-    if (wr == 0) __builtin_amdgcn_s_barrier();
+    if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-
     if (do_cs) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -1034,153 +1084,6 @@ __global__ __launch_bounds__(512, 2) void gemm8p_tn_group_kernel(const GemmGroup
     tn_tile(gg.g[p], idx - gg.first[p], smem);
 }
 
-int launch_tn(const GemmArgs& g, int nblocks, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_tn_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_done = true;
-    }
-    gemm8p_tn_kernel<<<nblocks, 512, LDS_BYTES, st>>>(g);
-    SC_LAUNCH_CHECK();
-    return 1;
-}
-
-// =====================================================================================================================
-// FP8 (OCP e4m3) TN variant (round 4): weight gradients dW[m, n] = sum_k A8[k, m] B8[k, n] with both operands token-major bytes
-// quantised with ONE scale per tensor (the reduction runs over the tokens, so a per-token scale cannot be pulled out of it).
-//   K tile = 128 tokens; half-tile image = [128 k][128 columns] bytes (16 KiB, 128-B rows): the ring, the DMA piece count and the
-//   phase schedule are byte-for-byte those of the bf16 TN kernel above, with twice the k per tile.
-//   Fragments: the MFMA (v_mfma_scale_f32_16x16x128_f8f6f4) wants, in lane (g = lane >> 4, r = lane & 15), the 32 consecutive k
-//   [32 g, 32 g + 32) of output row r, one per byte.  ds_read_b64_tr_b8 (layout probed with tools/micro/tr_b8_layout.hip: lane
-//   2 q + p of a 16-lane group supplies the address of (row q, byte columns 8 p .. 8 p + 7); lane i receives column i of rows
-//   0 .. 7) delivers 8 of them: four reads per fragment at k offsets 0, 8, 16, 24 (+1024 B each in the image).
-//   Swizzle: 16-byte chunk ^= ((k >> 1) & 3) | ((k >> 5) & 1) << 2 -- the four same-parity rows of an 8-row block and the two
-//   row blocks a 32-lane half reads land on eight different 16-byte bank windows; the per-lane swizzle term does not depend on
-//   which of the four reads it is, so they are immediate offsets off one address.
-//   C = a_scale_inv * b_scale_inv * sum (fp32 slabs as above); the fused bias gradient sums the e4m3 A fragments (x a_scale_inv).
-// Block scales of the f8f6f4 MFMA.  Unit scales two ways: E8M0 127 (= 2^0) in the scale registers of the SCALED opcode
-// (v_mfma_scale_..., a 16-byte encoding that loads the scales in front of every MFMA), or the constant 0, for which the compiler
-// selects the UNSCALED opcode v_mfma_f32_16x16x128_f8f6f4 (8-byte encoding, no scale load; the scales are implicitly one).
-// -DSC_F8_SCALED_OPCODE keeps the first form (A/B; tests/test_gpu_fp8.py's exact-integer tests pin the arithmetic of either).
-#ifdef SC_F8_SCALED_OPCODE
-#define SC_F8_UNIT_SCALE 0x7F7F7F7F
-#else
-#define SC_F8_UNIT_SCALE 0
-#endif
-typedef __attribute__((ext_vector_type(8))) int i32x8t;
-struct FragT8 {
-    union {
-        i32x8t v;               // the MFMA operand: 8 consecutive registers
-        u32x2 q[4];             // k blocks 0..7, 8..15, 16..23, 24..31 of this lane's group (one transposed read each)
-    };
-};
-template <int OFF>
-SC_DEVICE u32x2 tr8_asm(unsigned lds_addr) {
-    u32x2 r;
-    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
-    return r;
-}
-// Q = half-tile index inside one ring parity: its byte offset (<= 48 KiB) rides in the instruction's 16-bit offset field, so a
-// fragment needs ONE address register per ring parity instead of one per ring slot (with the slot folded into the address the
-// compiler keeps ~24 hoisted address registers and spills)
-template <int Q>
-SC_DEVICE void t8_read(unsigned addr, FragT8& f) {
-    f.q[0] = tr8_asm<Q * HALF>(addr);
-    f.q[1] = tr8_asm<Q * HALF + 1024>(addr);
-    f.q[2] = tr8_asm<Q * HALF + 2048>(addr);
-    f.q[3] = tr8_asm<Q * HALF + 3072>(addr);
-}
-SC_DEVICE void t8_wait2(FragT8 (&f)[2]) {          // retire every register the asm reads above wrote (see tn_wait4)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].v), "+v"(f[1].v) :: "memory");
-}
-SC_DEVICE void t8_wait4(FragT8 (&f)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].v), "+v"(f[1].v), "+v"(f[2].v), "+v"(f[3].v) :: "memory");
-}
-SC_DEVICE i32x8t t8_cat(const FragT8& f) { return f.v; }
-SC_DEVICE float t8_sum(const FragT8& f) {          // sum of this lane's 32 e4m3 values
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            const int v = (int)f.q[j][w];
-            s += __builtin_amdgcn_cvt_f32_fp8(v, 0) + __builtin_amdgcn_cvt_f32_fp8(v, 1) + __builtin_amdgcn_cvt_f32_fp8(v, 2) +
-                 __builtin_amdgcn_cvt_f32_fp8(v, 3);
-        }
-    return s;
-}
-
-struct StagerT8 {
-    // wave-uniform base (SGPRs) + 32-bit per-lane offset: the DMA takes the scalar-base addressing form and the eight source
-    // addresses cost 8 VGPRs instead of 16 (with 64-bit pointers the kernel spilled them and reloaded one before every DMA)
-    const unsigned char* base[4];
-    unsigned off[4];            // piece 0 of each half-tile kind; piece 1 is 64 k rows further: a scalar addend (step / 2)
-    long long step[4];          // bytes per K tile (128 source rows) for each half-tile kind
-    int nt;
-    int wave;
-};
-
-template <int D, int PH>
-SC_DEVICE void phase_t8(char* smem, unsigned lds0, const StagerT8& S, int t, const unsigned (&a_off)[4], const unsigned (&b_off)[2],
-                        FragT8 (&a)[4], FragT8 (&b0)[2], FragT8 (&b1)[2], f32x4 (&acc)[8][4], bool do_cs, int wc, float (&cs)[2]) {
-    constexpr unsigned pd = D * 4 * HALF;               // ring parity base, part of the (hoisted) address
-    if (PH == 1) { t8_read<1>(lds0 + pd + b_off[0], b0[0]); t8_read<1>(lds0 + pd + b_off[1], b0[1]); }
-    if (PH == 2) { t8_read<2>(lds0 + pd + b_off[0], b1[0]); t8_read<2>(lds0 + pd + b_off[1], b1[1]); }
-    if (PH == 1) {
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) t8_read<0>(lds0 + pd + a_off[ii], a[ii]);
-    }
-    if (PH == 3) {
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) t8_read<3>(lds0 + pd + a_off[ii], a[ii]);
-    }
-    constexpr int q = (PH + 1) & 3;
-    constexpr int DS = PH <= 2 ? (D ^ 1) : D;
-    const int ts = t + (PH <= 2 ? 1 : 2);
-    if (ts < S.nt) {
-        const unsigned char* kb = S.base[q] + ts * S.step[q];
-        unsigned o0 = S.off[q];
-        asm volatile("" : "+v"(o0));                      // keep (scalar base + 32-bit offset): a hoisted 64-bit sum costs 2 VGPRs each
-        dma16(kb + o0, smem + slot(DS, q) + S.wave * 1024);
-        dma16(kb + (S.step[q] >> 1) + o0, smem + slot(DS, q) + (8 + S.wave) * 1024);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    if (PH == 1) { t8_wait2(b0); t8_wait4(a); }
-    if (PH == 2) t8_wait2(b1);
-    if (PH == 3) t8_wait4(a);
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int mi = PH >= 3 ? 1 : 0;
-    constexpr int nj = (PH == 2 || PH == 3) ? 1 : 0;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-        const i32x8t af = t8_cat(a[ii]);
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-            acc[mi * 4 + ii][nj * 2 + jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                t8_cat(nj ? b1[jj] : b0[jj]), af, acc[mi * 4 + ii][nj * 2 + jj], 0, 0, 0, SC_F8_UNIT_SCALE, 0, SC_F8_UNIT_SCALE);
-        if ((PH == 1 || PH == 3) && do_cs && ii == wc) cs[mi] += t8_sum(a[ii]);     // fused bias gradient, as in the bf16 kernel
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-SC_DEVICE void ktile_t8(char* smem, unsigned lds0, const StagerT8& S, int t, const unsigned (&a_off)[4], const unsigned (&b_off)[2],
-                        FragT8 (&a)[4], FragT8 (&b0)[2], FragT8 (&b1)[2], f32x4 (&acc)[8][4], bool do_cs, int wc, float (&cs)[2]) {
-    phase_t8<D, 1>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_t8<D, 2>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_t8<D, 3>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-    phase_t8<D, 4>(smem, lds0, S, t, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-}
-
 // g.A / g.B: e4m3 bytes [K tokens][M] / [K][N], lda / ldb in BYTES; g.K tokens (k_per_split a multiple of 128);
 // g.a_scale / g.b_scale: ONE dequantisation factor each (device scalars)
 __global__ __launch_bounds__(512, 2) void gemm8p_tn_f8_kernel(const GemmArgs g) {
@@ -1192,18 +1095,15 @@ __global__ __launch_bounds__(512, 2) void gemm8p_tn_f8_kernel(const GemmArgs g) 
     const int wr = wave >> 2, wc = wave & 3;
     const int li = lane & 15, lg = lane >> 4;
 
-    int idx = sc_xcd_remap(blockIdx.x, gridDim.x);
-    const int tn = idx % g.ntn;
-    idx /= g.ntn;
-    const int tm = idx % g.ntm;
-    const int z = idx / g.ntm;
+    int z, tm, tn;
+    tile_decode(sc_xcd_remap(blockIdx.x, gridDim.x), g, z, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int kbeg = z * g.k_per_split;
     const int kend = min(g.K, kbeg + g.k_per_split);
-    const unsigned char* A8 = reinterpret_cast<const unsigned char*>(g.A);
-    const unsigned char* B8 = reinterpret_cast<const unsigned char*>(g.B);
+    const char* A8 = reinterpret_cast<const char*>(g.A);
+    const char* B8 = reinterpret_cast<const char*>(g.B);
 
-    StagerT8 S;
+    StagerTN S;
     S.nt = (kend - kbeg) / BK8;
     S.wave = wave;
     S.step[0] = S.step[3] = (long long)BK8 * g.lda;
@@ -1222,15 +1122,15 @@ __global__ __launch_bounds__(512, 2) void gemm8p_tn_f8_kernel(const GemmArgs g) 
     }
     S.base[0] = S.base[3] = A8 + (size_t)kbeg * g.lda;
     S.base[1] = S.base[2] = B8 + (size_t)kbeg * g.ldb;
-    const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem;
-    unsigned a_off[4], b_off[2];
+
+    FragOffs<OpsTN8> O;
     {
         const int sw = ((li >> 2) & 3) | ((lg & 1) << 2);                // swizzle term of rows 32 lg + 8 j + (li >> 1), any j
         const int row = (32 * lg + (li >> 1)) * 128 + (li & 1) * 8;
 #pragma unroll
-        for (int ii = 0; ii < 4; ++ii) a_off[ii] = row + (((wr * 4 + ii) ^ sw) << 4);
+        for (int ii = 0; ii < 4; ++ii) O.a[ii] = row + (((wr * 4 + ii) ^ sw) << 4);
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) b_off[jj] = row + (((wc * 2 + jj) ^ sw) << 4);
+        for (int jj = 0; jj < 2; ++jj) O.b[jj] = row + (((wc * 2 + jj) ^ sw) << 4);
     }
 
     f32x4 acc[8][4];
@@ -1241,31 +1141,27 @@ __global__ __launch_bounds__(512, 2) void gemm8p_tn_f8_kernel(const GemmArgs g) 
     const bool do_cs = g.colsum != nullptr && tn == 0;
     float cs[2] = {0.f, 0.f};
 
+    // prologue: the first six half-tiles (all of K tile 0, A0 and B0 of K tile 1)
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ts = s >> 2, q = s & 3;
-        if (ts < S.nt) {
-            const unsigned char* kb = S.base[q] + ts * S.step[q];
-            dma16(kb + S.off[q], smem + slot(ts & 1, q) + wave * 1024);
-            dma16(kb + (S.step[q] >> 1) + S.off[q], smem + slot(ts & 1, q) + (8 + wave) * 1024);
-        }
+        if (ts < S.nt) OpsTN8::stage<false>(S, q, ts, smem + slot(ts & 1, q));
     }
     if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    FragT8 a[4], b0[2], b1[2];
+    Frags<OpsTN8> F;
     for (int kt = 0; kt < S.nt; kt += 2) {
-        ktile_t8<0>(smem, lds0, S, kt, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
-        if (kt + 1 < S.nt) ktile_t8<1>(smem, lds0, S, kt + 1, a_off, b_off, a, b0, b1, acc, do_cs, wc, cs);
+        ktile<OpsTN8, 0>(smem, S, kt, O, F, acc, do_cs, wc, cs);
+        if (kt + 1 < S.nt) ktile<OpsTN8, 1>(smem, S, kt + 1, O, F, acc, do_cs, wc, cs);
     }
-    if (wr == 0) __builtin_amdgcn_s_barrier();
+    if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-
     const float sa = g.a_scale ? *g.a_scale : 1.0f, sb = g.b_scale ? *g.b_scale : 1.0f;
     if (do_cs) {
 #pragma unroll
@@ -1298,84 +1194,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_tn_f8_kernel(const GemmArgs g) 
     }
 }
 
-// =====================================================================================================================
-// FP8 (OCP e4m3) NT variant: the same tile, ring, phase schedule and epilogues on one-byte operands.  A half-tile row
-// is still 128 bytes, i.e. 128 k values instead of 64, so the staging stream, swizzle and waits are byte-for-byte the
-// bf16 kernel's; the caller passes K / 2, lda / 2, ldb / 2 ("bf16 elements") and the MFMA section issues ONE
-// v_mfma_scale_f32_16x16x128_f8f6f4 per fragment pair where the bf16 kernel issues two 16x16x32: half the MFMA count
-// for twice the k per tile = 2x the matrix rate.  Operand layout (probed with integer data, tools/micro/
-// mfma_fp8_layout.hip): lane (g = lane >> 4, r = lane & 15) supplies row r and the 32 consecutive k of bytes
-// [32 g, 32 g + 32) of the 128-byte row = the two 16-byte chunks 2g, 2g + 1; the block scales are E8M0 1.0 -- the real
-// scales are per-row floats applied to the accumulators before the epilogue:
-//     C[m][n] = a_scale[m] * b_scale[n] * sum_k A8[m][k] B8[n][k]   (+ bias, residual, GELU as in the bf16 kernel).
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-struct Frag8 {
-    union { i32x8 v; u32x4 h[2]; };
-};
-
-template <int D, int PH>
-SC_DEVICE void phase_f8(char* smem, const Stager& S, int t, const int (&a_off)[2], const int (&b_off)[2], Frag8 (&a)[4],
-                        Frag8 (&b0)[2], Frag8 (&b1)[2], f32x4 (&acc)[8][4]) {
-    if (PH == 1) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b0[jj].h[kk] = *reinterpret_cast<const u32x4*>(smem + slot(D, 1) + b_off[kk] + jj * 2048);
-    }
-    if (PH == 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                b1[jj].h[kk] = *reinterpret_cast<const u32x4*>(smem + slot(D, 2) + b_off[kk] + jj * 2048);
-    }
-    if (PH == 1 || PH == 3) {
-        constexpr int sl = slot(D, PH == 1 ? 0 : 3);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii)
-                a[ii].h[kk] = *reinterpret_cast<const u32x4*>(smem + sl + a_off[kk] + ii * 2048);
-    }
-    constexpr int q = (PH + 1) & 3;
-    constexpr int DS = PH <= 2 ? (D ^ 1) : D;
-    const int ts = t + (PH <= 2 ? 1 : 2);
-    if (ts < S.nt) {
-        dma16(S.src[q][0] + (size_t)ts * BK, smem + slot(DS, q) + S.wave * 1024);
-        dma16(S.src[q][1] + (size_t)ts * BK, smem + slot(DS, q) + (8 + S.wave) * 1024);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int mi = PH >= 3 ? 1 : 0;
-    constexpr int nj = (PH == 2 || PH == 3) ? 1 : 0;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-            acc[mi * 4 + ii][nj * 2 + jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                nj ? b1[jj].v : b0[jj].v, a[ii].v, acc[mi * 4 + ii][nj * 2 + jj], 0, 0, 0, SC_F8_UNIT_SCALE, 0, SC_F8_UNIT_SCALE);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int D>
-SC_DEVICE void ktile_f8(char* smem, const Stager& S, int t, const int (&a_off)[2], const int (&b_off)[2], Frag8 (&a)[4],
-                        Frag8 (&b0)[2], Frag8 (&b1)[2], f32x4 (&acc)[8][4]) {
-    phase_f8<D, 1>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase_f8<D, 2>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase_f8<D, 3>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-    phase_f8<D, 4>(smem, S, t, a_off, b_off, a, b0, b1, acc);
-}
-
-// g.K / lda / ldb are in 2-byte units (see above); g.a_scale [M] and g.b_scale [N] are the dequantisation factors
+// FP8 NT (OpsNT8 above): g.K / lda / ldb are in 2-byte units; g.a_scale [M] and g.b_scale [N] are the dequantisation factors
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1395,8 +1214,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
     S.wave = wave;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int r = (p * 8 + wave) * 8 + (lane >> 3);
-        const int lc = (lane & 7) ^ ((r >> 1) & 7);
+        const int r = (p * 8 + wave) * 8 + (lane >> 3);          // row of the half-tile image, 128 B per row
+        const int lc = (lane & 7) ^ ((r >> 1) & 7);              // logical 16-byte chunk stored at physical lane&7
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int ga = min(m0 + (r >> 6) * 128 + h * 64 + (r & 63), g.M - 1);
@@ -1405,7 +1224,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
             S.src[h ? 2 : 1][p] = g.B + (size_t)gb * g.ldb + lc * 8;
         }
     }
-    int a_off[2], b_off[2];
+    FragOffs<OpsNT8> O;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         // Which two 16-byte chunks of the 128-byte row lane group lg takes is free -- the MFMA sums over all 128 k, and A and B
@@ -1415,35 +1234,35 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
         // SQ_LDS_BANK_CONFLICT 29.5 M cycles against the bf16 kernel's 4.2 M on the same bytes (profiles/r06_fp8_ktile_probe.txt).
         // Conflict-free needs c(lg, kk) ^ c(lg ^ 1, kk) in {1, 6, 7}: c = 4 (lg >> 1) + 2 kk + (lg & 1).
         const int coff = (((lg >> 1) * 4 + 2 * kk + (lg & 1)) ^ ((li >> 1) & 7)) << 4;
-        a_off[kk] = (wr * 64 + li) * 128 + coff;
-        b_off[kk] = (wc * 32 + li) * 128 + coff;
+        O.a[kk] = (wr * 64 + li) * 128 + coff;
+        O.b[kk] = (wc * 32 + li) * 128 + coff;
     }
+
     f32x4 acc[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // prologue: the first six half-tiles (all of K tile 0, A0 and B0 of K tile 1)
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ts = s >> 2, q = s & 3;
-        if (ts < S.nt) {
-            dma16(S.src[q][0] + (size_t)ts * BK, smem + slot(ts & 1, q) + wave * 1024);
-            dma16(S.src[q][1] + (size_t)ts * BK, smem + slot(ts & 1, q) + (8 + wave) * 1024);
-        }
+        if (ts < S.nt) OpsNT8::stage(S, q, ts, smem + slot(ts & 1, q));
     }
     if (S.nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();                   // waves 4-7 run one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
-    Frag8 a[4], b0[2], b1[2];
+    Frags<OpsNT8> F;
     for (int kt = 0; kt < S.nt; kt += 2) {
-        ktile_f8<0>(smem, S, kt, a_off, b_off, a, b0, b1, acc);
-        if (kt + 1 < S.nt) ktile_f8<1>(smem, S, kt + 1, a_off, b_off, a, b0, b1, acc);
+        ktile<OpsNT8, 0>(smem, S, kt, O, F, acc);
+        if (kt + 1 < S.nt) ktile<OpsNT8, 1>(smem, S, kt + 1, O, F, acc);
     }
-    if (wr == 0) __builtin_amdgcn_s_barrier();
+    if (wr == 0) __builtin_amdgcn_s_barrier();                   // re-align the two wave groups
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 
@@ -1463,7 +1282,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
             for (int j = 0; j < 4; ++j) acc[i][j] *= sb[j] * sa;
         }
     }
-    if (EPI == SC_EPI_GELU_GRAD_PAIR && g.gelu_lut != nullptr) {     // GELU by table, as in gemm8p_kernel
+    if (EPI == SC_EPI_GELU_GRAD_PAIR && g.gelu_lut != nullptr) {
+        // the table moves into the dead operand ring (behind the eight 4-KiB strips) while the first strip pass is packed
         unsigned* lut = reinterpret_cast<unsigned*>(smem + 8 * 4096);
         for (int c = t; c < SC_GELU_LUT_N / 4; c += 512)
             reinterpret_cast<u32x4*>(lut)[c] = reinterpret_cast<const u32x4*>(g.gelu_lut)[c];
@@ -1494,17 +1314,59 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
     }
 }
 
-template <int EPI>
-int launch_f8(const GemmArgs& g, int nblocks, hipStream_t st) {
+// Host side.  Launch of one of this file's 512-thread kernels with `lds` bytes of dynamic LDS; the kernel's limit (lds_max) is
+// raised on its first launch, once per kernel: Kernel is a template argument, so every kernel has its own flag.
+template <auto Kernel, class... Args>
+int launch_lds(int grid, int lds_max, int lds, hipStream_t st, const Args&... args) {
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_f8_kernel<EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         attr_done = true;
     }
-    gemm8p_f8_kernel<EPI><<<nblocks, 512, LDS_BYTES, st>>>(g);
+    Kernel<<<grid, 512, lds, st>>>(args...);
     SC_LAUNCH_CHECK();
     return 1;
+}
+
+// f(std::integral_constant<int, EPI>) for the run-time epilogue `epi`; 0 when there is no such epilogue
+template <class F>
+int epi_dispatch(int epi, F f) {
+#define SC_CASE(EPI) \
+    if (epi == EPI) return f(std::integral_constant<int, EPI>{});
+    SC_CASE(SC_EPI_BF16)
+    SC_CASE(SC_EPI_BF16_BIAS)
+    SC_CASE(SC_EPI_F32_BIAS_RES)
+    SC_CASE(SC_EPI_GELU_PAIR)
+    SC_CASE(SC_EPI_BF16_DGELU)
+    SC_CASE(SC_EPI_F32)
+    SC_CASE(SC_EPI_BF16_BIAS_RES)
+    SC_CASE(SC_EPI_GELU_GRAD_PAIR)
+    SC_CASE(SC_EPI_BF16_MUL_AUX)
+#undef SC_CASE
+    return 0;
+}
+
+// Split-K plan: `req` slices (one without slabs to reduce through) over ktiles K tiles, evened out so that no slice is empty.
+// Returns the slice count; *tiles_per = K tiles per slice.
+int splitk_plan(int ktiles, int req, bool has_slabs, int* tiles_per) {
+    int splitk = (req < 1 || !has_slabs) ? 1 : req;
+    if (splitk > ktiles) splitk = ktiles;
+    *tiles_per = (ktiles + splitk - 1) / splitk;
+    return (ktiles + *tiles_per - 1) / *tiles_per;
+}
+// The plan for K tiles of bk, written into g; with more than one slice the output goes to the slabs.  false = split-K asked
+// of an output that is not dense (ldc != N)
+bool splitk_set(GemmArgs& g, int bk, int req, float* slabs, bool has_slabs) {
+    int tiles_per = 0;
+    g.splitk = splitk_plan(g.K / bk, req, has_slabs, &tiles_per);
+    g.k_per_split = tiles_per * bk;
+    g.slab_stride = 0;
+    if (g.splitk > 1) {
+        if (g.ldc != g.N) return false;
+        g.C = slabs;
+        g.slab_stride = (long long)g.M * g.N;
+    }
+    return true;
 }
 
 }  // namespace
@@ -1523,16 +1385,9 @@ int sc_gemm8p_fp8(int epi, GemmArgs& g, hipStream_t st) {
         if (!(sw && sw[0] == '0')) g.gelu_lut = sc_gelu_lut_device(st, g.act);
     }
     sc_gemm_note_path(SC_GEMM_PATH_FP8_NT, g.gelu_lut != nullptr, 0, 1, SC_GEMM_COLSUM_NONE);
-    if (epi == SC_EPI_BF16) return launch_f8<SC_EPI_BF16>(g, nblocks, st);
-    if (epi == SC_EPI_BF16_BIAS) return launch_f8<SC_EPI_BF16_BIAS>(g, nblocks, st);
-    if (epi == SC_EPI_F32_BIAS_RES) return launch_f8<SC_EPI_F32_BIAS_RES>(g, nblocks, st);
-    if (epi == SC_EPI_GELU_PAIR) return launch_f8<SC_EPI_GELU_PAIR>(g, nblocks, st);
-    if (epi == SC_EPI_BF16_DGELU) return launch_f8<SC_EPI_BF16_DGELU>(g, nblocks, st);
-    if (epi == SC_EPI_F32) return launch_f8<SC_EPI_F32>(g, nblocks, st);
-    if (epi == SC_EPI_BF16_BIAS_RES) return launch_f8<SC_EPI_BF16_BIAS_RES>(g, nblocks, st);
-    if (epi == SC_EPI_GELU_GRAD_PAIR) return launch_f8<SC_EPI_GELU_GRAD_PAIR>(g, nblocks, st);
-    if (epi == SC_EPI_BF16_MUL_AUX) return launch_f8<SC_EPI_BF16_MUL_AUX>(g, nblocks, st);
-    return 0;
+    return epi_dispatch(epi, [&](auto E) {
+        return launch_lds<&gemm8p_f8_kernel<decltype(E)::value>>(nblocks, LDS_BYTES, LDS_BYTES, st, g);
+    });
 }
 
 // Grouped TN launch (sc_gemm_wgrad_group): every g[p] describes dW_p[M_p, N_p] = A_p[K, M_p]^T . B_p[K, N_p] with the SAME K;
@@ -1546,11 +1401,8 @@ int sc_gemm8p_tn_group_plan(const GemmArgs* g, int n, int splitk_req, int* split
         if (g[p].K != K || g[p].M < 256 || g[p].N < 192 || (g[p].M % 8) != 0 || (g[p].N % 8) != 0) return 0;
         if ((long long)g[p].M * g[p].N < 256LL * 256 * 8 || g[p].ldc != g[p].N) return 0;
     }
-    const int ktiles = K / BK;
-    int splitk = splitk_req < 1 ? 1 : splitk_req;
-    if (splitk > ktiles) splitk = ktiles;
-    const int tiles_per = (ktiles + splitk - 1) / splitk;
-    *splitk_out = (ktiles + tiles_per - 1) / tiles_per;
+    int tiles_per = 0;
+    *splitk_out = splitk_plan(K / BK, splitk_req, true, &tiles_per);
     *k_per_split = tiles_per * BK;
     return 1;
 }
@@ -1564,19 +1416,11 @@ int sc_gemm8p_tn_group_launch(const GemmArgs* g, int n, hipStream_t st) {
         total += g[p].ntm * g[p].ntn * g[p].splitk;
     }
     for (int p = n; p <= SC_WGRAD_GROUP_MAX; ++p) gg.first[p] = total;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_tn_group_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_done = true;
-    }
     bool sums = false;
     for (int p = 0; p < n; ++p) sums = sums || g[p].colsum != nullptr;
     sc_gemm_note_path(SC_GEMM_PATH_TN8P_GROUP, 0, 0, g[0].splitk, sums ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
     sc_gemm_note_group(SC_GEMM_GROUP_ONE_LAUNCH);
-    gemm8p_tn_group_kernel<<<total, 512, LDS_BYTES, st>>>(gg);
-    SC_LAUNCH_CHECK();
-    return 1;
+    return launch_lds<&gemm8p_tn_group_kernel>(total, LDS_BYTES, LDS_BYTES, st, gg);
 }
 
 // fp8 TN weight gradient: g.A / g.B e4m3 bytes [K][M] / [K][N] (lda / ldb in bytes), g.a_scale / g.b_scale device scalars, g.C fp32;
@@ -1586,30 +1430,9 @@ int sc_gemm8p_tn_fp8(GemmArgs& g, int splitk_req, float* slabs, hipStream_t st) 
     if ((g.lda % 16) != 0 || (g.ldb % 16) != 0) return 0;
     g.ntm = (g.M + BM - 1) / BM;
     g.ntn = (g.N + BN - 1) / BN;
-    const int ktiles = g.K / 128;
-    int splitk = splitk_req < 1 ? 1 : splitk_req;
-    if (slabs == nullptr) splitk = 1;
-    if (splitk > ktiles) splitk = ktiles;
-    const int tiles_per = (ktiles + splitk - 1) / splitk;
-    splitk = (ktiles + tiles_per - 1) / tiles_per;
-    g.splitk = splitk;
-    g.k_per_split = tiles_per * 128;
-    g.slab_stride = 0;
-    if (splitk > 1) {
-        if (g.ldc != g.N) return 0;
-        g.C = slabs;
-        g.slab_stride = (long long)g.M * g.N;
-    }
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_tn_f8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_BYTES);
-        attr_done = true;
-    }
-    sc_gemm_note_path(SC_GEMM_PATH_FP8_TN, 0, 0, splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
-    gemm8p_tn_f8_kernel<<<g.ntm * g.ntn * splitk, 512, LDS_BYTES, st>>>(g);
-    SC_LAUNCH_CHECK();
-    return 1;
+    if (!splitk_set(g, 128, splitk_req, slabs, slabs != nullptr)) return 0;
+    sc_gemm_note_path(SC_GEMM_PATH_FP8_TN, 0, 0, g.splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
+    return launch_lds<&gemm8p_tn_f8_kernel>(g.ntm * g.ntn * g.splitk, LDS_BYTES, LDS_BYTES, st, g);
 }
 
 // Which launches take the column-group walk by default (measured per launch class: profiles/r05_gemm_colgroup.txt).
@@ -1693,23 +1516,12 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     g.ntm = (g.M + BM - 1) / BM;
     g.ntn = (g.N + BN - 1) / BN;
     const int ktiles = g.K / BK;
-    int splitk = splitk_req < 1 ? 1 : splitk_req;
-    if (epi != SC_EPI_F32 || slabs == nullptr) splitk = 1;
-    if (splitk > ktiles) splitk = ktiles;
-    int tiles_per = (ktiles + splitk - 1) / splitk;
-    splitk = (ktiles + tiles_per - 1) / tiles_per;
-    g.splitk = splitk;
-    g.k_per_split = tiles_per * BK;
-    g.slab_stride = 0;
-    if (splitk > 1) {
-        if (g.ldc != g.N) return 0;
-        g.C = slabs;
-        g.slab_stride = (long long)g.M * g.N;
-    }
+    if (!splitk_set(g, BK, splitk_req, slabs, epi == SC_EPI_F32 && slabs != nullptr)) return 0;
+    const int splitk = g.splitk;
     const int nblocks = g.ntm * g.ntn * splitk;
     if (mode == SC_GEMM_TN) {
         sc_gemm_note_path(SC_GEMM_PATH_TN8P, 0, 0, splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
-        return launch_tn(g, nblocks, st);
+        return launch_lds<&gemm8p_tn_kernel>(nblocks, LDS_BYTES, LDS_BYTES, st, g);
     }
     // GELU by table: only the non-persistent kernel has LDS to spare for it (the persistent one fills all 160 KiB)
     if (epi == SC_EPI_GELU_GRAD_PAIR) {
@@ -1719,12 +1531,14 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     // persistent walk of the tile list for the store-only bf16 epilogues once there is more than one round of tiles
     static const bool persist = !(getenv("SC_GEMM_PERSIST") && getenv("SC_GEMM_PERSIST")[0] == '0');
     if (g.gelu_lut == nullptr && persist && splitk == 1 && nblocks >= 1024 && ktiles >= 3) {      // >= 4 rounds of tiles (measured: +7 % at 7 rounds, -3 % at 2.3)
-        if (epi == SC_EPI_BF16 || epi == SC_EPI_BF16_BIAS || epi == SC_EPI_GELU_PAIR || epi == SC_EPI_GELU_GRAD_PAIR)
+        if (epi == SC_EPI_BF16 || epi == SC_EPI_BF16_BIAS || epi == SC_EPI_GELU_PAIR || epi == SC_EPI_GELU_GRAD_PAIR) {     // GELU pair: +1.5 % at 9.2 rounds
             sc_gemm_note_path(SC_GEMM_PATH_NT8P_PERSISTENT, 0, 0, 1, SC_GEMM_COLSUM_NONE);
-        if (epi == SC_EPI_BF16) return launch_persistent<SC_EPI_BF16>(g, nblocks, st);
-        if (epi == SC_EPI_BF16_BIAS) return launch_persistent<SC_EPI_BF16_BIAS>(g, nblocks, st);
-        if (epi == SC_EPI_GELU_PAIR) return launch_persistent<SC_EPI_GELU_PAIR>(g, nblocks, st);      // +1.5 % at 9.2 rounds
-        if (epi == SC_EPI_GELU_GRAD_PAIR) return launch_persistent<SC_EPI_GELU_GRAD_PAIR>(g, nblocks, st);
+            const int grid = nblocks < 256 ? nblocks : 256, lds = RING + 8 * 4096;
+            if (epi == SC_EPI_BF16) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16>>(grid, lds, lds, st, g, nblocks);
+            if (epi == SC_EPI_BF16_BIAS) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16_BIAS>>(grid, lds, lds, st, g, nblocks);
+            if (epi == SC_EPI_GELU_PAIR) return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_PAIR>>(grid, lds, lds, st, g, nblocks);
+            return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_GRAD_PAIR>>(grid, lds, lds, st, g, nblocks);
+        }
     }
     // Tile walk of the non-persistent kernel: SC_GEMM_COLGROUP="<epi>:<Gc>[,<epi>:<Gc>...]" (A/B switch, read per call)
     // walks the named epilogues' launches in column groups of Gc tiles inside per-XCD row bands (sc_tile_colgroup).
@@ -1764,20 +1578,10 @@ int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, 
     sc_last_tail[0] = g.tail_first > 0 ? g.tail_first : nblocks;
     sc_last_tail[1] = g.tail_rem;
     sc_gemm_note_path(SC_GEMM_PATH_NT8P, g.gelu_lut != nullptr, g.col_group, splitk, SC_GEMM_COLSUM_NONE);
-    int rc = 0;
-#define SC_CASE(EPI) \
-    if (epi == EPI) rc = launch<EPI>(g, grid, st);
-    SC_CASE(SC_EPI_BF16)
-    SC_CASE(SC_EPI_BF16_BIAS)
-    SC_CASE(SC_EPI_F32_BIAS_RES)
-    SC_CASE(SC_EPI_GELU_PAIR)
-    SC_CASE(SC_EPI_BF16_DGELU)
-    SC_CASE(SC_EPI_F32)
-    SC_CASE(SC_EPI_BF16_BIAS_RES)
-    SC_CASE(SC_EPI_GELU_GRAD_PAIR)
-    SC_CASE(SC_EPI_BF16_MUL_AUX)
-#undef SC_CASE
-    return rc;
+    // a launch with half tiles needs their nine-slot ring
+    const int lds_max = LDS_BYTES > HRING ? LDS_BYTES : HRING;
+    const int lds = g.tail_first > 0 ? lds_max : LDS_BYTES;
+    return epi_dispatch(epi, [&](auto E) { return launch_lds<&gemm8p_kernel<decltype(E)::value>>(grid, lds_max, lds, st, g); });
 }
 
 // device copy of the GELU table, one per device and activation, filled on first use by the formula itself (sc_gemm_common.h)

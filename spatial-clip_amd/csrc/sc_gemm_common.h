@@ -59,6 +59,31 @@ struct GemmArgs {
     int tail_rem = 0;
 };
 
+// ---- operand movement shared by the 256x256 kernels (sc_gemm256.hip, sc_gemm8p.hip) ----
+typedef const __attribute__((address_space(1))) void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+
+SC_DEVICE void dma16(const void* src, char* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
+}
+
+// ds_read_b64_tr_b16 through inline asm.  In front of the builtin form hipcc places `s_waitcnt vmcnt(0)` whenever an
+// LDS-DMA is in flight (it cannot see that the DMA fills the OTHER stage), which serialises the prefetch of K tile
+// i+1 with the fragment reads of tile i; plain ds_read_b128 (the NT path) does not get that wait.  The asm form is
+// invisible to the waitcnt pass, so the lgkmcnt waits it would have placed are written by hand (tr_wait in sc_gemm256.hip,
+// the wait_a / wait_b of the TN operand policies in sc_gemm8p.hip).
+template <int OFF>
+SC_DEVICE u32x2 tr16_asm(unsigned lds_addr) {
+    u32x2 r;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
+    return r;
+}
+SC_DEVICE bf16x8 tr_cat(u32x2 lo, u32x2 hi) {
+    union { u32x4 u; bf16x8 b; } c;
+    c.u = (u32x4){lo[0], lo[1], hi[0], hi[1]};
+    return c.b;
+}
+
 // (tm, tn) of remapped tile index idx under the column-group walk (splitk == 1)
 SC_DEVICE void sc_tile_colgroup(int idx, const GemmArgs& g, int& tm, int& tn) {
     const int band_tiles = g.band_rows * g.ntn;
