@@ -382,6 +382,28 @@ int sc_png_decode(const void* files, const long long* offsets, int B, void* out_
                   void* stream);
 int sc_augment_tiles(const void* src_u8_hwc, int B, int H, int W, const float* params12, float* out_nchw, int S,
                      const float* mean3_host, const float* std3_host, void* stream);
+/* sc_augment_tiles_ex: the same transform with the rest of the reference's AugmentationCfg (timm create_transform,
+ * src/open_clip/transform.py:58-66,161-190), every step PIL's 8-bit arithmetic: crop + BICUBIC resize, horizontal flip,
+ * vertical flip, ColorJitter as a sequence of 0..4 ops that may hold hue (adjust_hue on a PIL image: RGB -> HSV, H += shift in
+ * uint8, HSV -> RGB with Convert.c's rounding), skipped as a whole when RandomApply(p = color_jitter_prob) said so,
+ * RandomGrayscale (convert("L") in three channels), ToTensor, Normalize, then RandomErasing (mode "const": boxes of 0.0 in
+ * the normalised output).  `params` is a HOST pointer to B rows of `param_stride` >= SC_AUG_ROW floats; the call checks
+ * them, stages them and copies them to the device on `stream` itself (it never waits for `stream`).  Row layout:
+ *    0..3   x0, y0, crop_w, crop_h            4..6   brightness, contrast, saturation factors       7   order code 0..5
+ *    8      horizontal flip (> 0.5)            9      vertical flip (> 0.5)
+ *   10      hue factor f in [-0.5, 0.5]; the shift is (uint8)(int32)((double)f * 255)
+ *   11      grayscale (> 0.5)                 12      1 = the jitter is left out for this sample
+ *   13      number of jitter ops n: 0 = the rule of the 12-float row (brightness, contrast, saturation in the order of
+ *           column 7); 1..4 = the ops of columns 14..14+n-1 in that order, codes 0 brightness, 1 contrast, 2 saturation,
+ *           3 hue, each at most once
+ *   18      number of erase boxes 0..4        19      reserved (0)
+ *   20+4k   top, left, height, width of box k, in output pixels, inside the S x S output
+ * A 12-float row of sc_augment_tiles extended with zeros gives the bytes sc_augment_tiles gives.  Rejected with
+ * sc_last_error set and nothing launched or written: more than 4 ops or boxes, an op code outside 0..3 or used twice, a box
+ * that is empty or not inside the output, a hue factor outside [-0.5, 0.5], param_stride < SC_AUG_ROW. */
+#define SC_AUG_ROW 36
+int sc_augment_tiles_ex(const void* src_u8_hwc, int B, int H, int W, const float* params_host, int param_stride,
+                        float* out_nchw, int S, const float* mean3_host, const float* std3_host, void* stream);
 
 /* h = gelu(u) on contiguous bf16 (exact-erf GELU, the formula and input of the fused GEMM epilogue: bit-identical to the
  * epilogue's second output).  Used by the activation-recomputation mode (open_clip's CLIP.set_grad_checkpointing,

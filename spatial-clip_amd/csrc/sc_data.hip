@@ -4,14 +4,21 @@
 //                     (docs/spatial_clip_data_pipeline.html "Step 1": KNN inside the same tissue sample,
 //                     weight = 1 / (distance + 1e-6), alpha = weight / sum(weights); the Gaussian variant of
 //                     notebooks/d1_dataset_construct_cw.ipynb is selectable)
-//   sc_augment_tiles  RandomResizedCrop(scale, ratio) -> bilinear resize -> ColorJitter(brightness, contrast,
-//                     saturation in a per-sample order) -> Normalize(mean, std) on decoded uint8 tiles
+//   sc_augment_tiles  RandomResizedCrop(scale, ratio) -> bicubic resize -> horizontal flip -> ColorJitter(brightness,
+//                     contrast, saturation in a per-sample order) -> Normalize(mean, std) on decoded uint8 tiles
 //                     (configs/model/spatial_clip.yaml:12-17 aug_cfg; src/open_clip/constants.py:1-2 mean / std)
+//   sc_augment_tiles_ex  the rest of AugmentationCfg as timm's create_transform orders it (src/open_clip/transform.py:58-66,
+//                     161-190): vertical flip, hue inside the jitter sequence, color_jitter_prob, RandomGrayscale,
+//                     RandomErasing; one kernel body, two instantiations
 // Random draws stay on the host (one small parameter row per sample), so a run is reproducible from its seed and the
 // kernels are pure functions of their inputs.  Both are HBM-bound byte movers: coalesced reads of the source rows,
 // one pass for the statistics the contrast step needs, one pass that writes the normalised fp32 NCHW tile.
+#include <mutex>
+#include <string.h>
+
 #include "sc_common.h"
 #include "sc_kernels.h"
+#include "sc_color_core.h"
 
 namespace {
 
@@ -65,11 +72,14 @@ __global__ __launch_bounds__(256) void knn_alpha_kernel(const float* __restrict_
     }
 }
 
-struct AugParams {          // one row of 12 floats per sample
-    float x0, y0, cw, ch;   // crop box in source pixels
+// One parameter row per sample: the 12 floats of sc_augment_tiles, or the SC_AUG_ROW floats of sc_augment_tiles_ex
+// (include/spatial_clip_hip.h documents both; columns 9.. of a 12-float row read as 0)
+constexpr int kAugRow = SC_AUG_ROW;
+enum { kOpBrightness = 0, kOpContrast = 1, kOpSaturation = 2, kOpHue = 3 };
+struct Jitter {
     float b, c, s;          // brightness / contrast / saturation factors (1 = identity)
-    float order;            // permutation code 0..5 of (brightness, contrast, saturation)
-    float flip, pad0, pad1, pad2;
+    int shift;              // hue: what adjust_hue adds to the H channel, 0..255
+    int seq, n;             // the ops in the order they run, two bits each from bit 0, and how many
 };
 
 // ---- What the reference's train transform does to a tile (src/open_clip/transform.py:186-204 with `use_timm: true`,
@@ -125,46 +135,53 @@ SC_DEVICE int clip8(int ss) {
     ss >>= kResampleBits;
     return ss < 0 ? 0 : (ss > 255 ? 255 : ss);
 }
-SC_DEVICE int pil_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
-// Image.blend(degenerate d, image v, alpha) on one 8-bit value (float32 arithmetic without contraction, truncation)
-SC_DEVICE int pil_blend(int d, int v, float alpha) {
-    const float t = __fadd_rn((float)d, __fmul_rn(alpha, (float)(v - d)));
-    if (alpha >= 0.f && alpha <= 1.0f) return (int)t & 255;
-    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
-}
-// ops 0 = brightness, 1 = contrast (degenerate = mean L of the whole image at that point), 2 = saturation
-SC_DEVICE void apply_op(int op, const AugParams& P, int mean_l, int (&v)[3]) {
-    if (op == 0) {
+using sc_color::pil_blend;
+using sc_color::pil_luma;
+template <bool EX>
+SC_DEVICE void apply_op(int op, const Jitter& J, int mean_l, int (&v)[3]) {
+    if (op == kOpBrightness) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(0, v[c], P.b);
-    } else if (op == 1) {
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(0, v[c], J.b);
+    } else if (op == kOpContrast) {      // degenerate = mean L of the whole image at that point
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(mean_l, v[c], P.c);
-    } else {
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(mean_l, v[c], J.c);
+    } else if (!EX || op == kOpSaturation) {
         const int g = pil_luma(v[0], v[1], v[2]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = pil_blend(g, v[c], P.s);
+        for (int c = 0; c < 3; ++c) v[c] = pil_blend(g, v[c], J.s);
+    } else {
+        sc_color::pil_hue(J.shift, v[0], v[1], v[2]);
+    }
+}
+// the first `n` ops of the sequence (n <= J.n)
+template <bool EX>
+SC_DEVICE void apply_seq(const Jitter& J, int n, int mean_l, int (&v)[3]) {
+    if (EX) {
+        for (int k = 0; k < n; ++k) apply_op<EX>((J.seq >> (2 * k)) & 3, J, mean_l, v);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < n) apply_op<EX>((J.seq >> (2 * k)) & 3, J, mean_l, v);
     }
 }
 __constant__ int kPerm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
 
 // One workgroup per sample.  LDS: coefficient tables of both axes (int32 [S][T] + xmin / count per output position) and the
 // 8-bit intermediate image of the horizontal pass for one channel ([crop_h][S]).  The resized 8-bit image is parked in the
-// output tensor (as floats 0..255, flip applied on the way in) between the passes; the last pass overwrites it in place.
+// output tensor (as floats 0..255, flips applied on the way in) between the passes; the last pass overwrites it in place.
+// EX = false reads 12-float rows (crop, three factors, order code, horizontal flip); EX = true reads the extended row:
+// vertical flip, a jitter sequence of 0..4 ops with hue, the jitter switch, grayscale and erase boxes as well.
+template <bool EX>
 __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __restrict__ src, int H, int W,
-                                                       const float* __restrict__ params, float* __restrict__ out, int S, int T,
-                                                       float m0, float m1, float m2, float s0, float s1, float s2) {
+                                                       const float* __restrict__ params, int stride, float* __restrict__ out,
+                                                       int S, int T, float m0, float m1, float m2, float s0, float s1, float s2) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ long long red[16];
     const int b = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
-    AugParams P;
-    {
-        const float* p = params + (long long)b * 12;
-        P.x0 = p[0]; P.y0 = p[1]; P.cw = p[2]; P.ch = p[3]; P.b = p[4]; P.c = p[5]; P.s = p[6]; P.order = p[7]; P.flip = p[8];
-    }
+    const float* p = params + (long long)b * stride;
     // integer crop box inside the tile (RandomResizedCrop draws integers; clamp defensively)
-    int cw = min(max((int)P.cw, 1), W), ch = min(max((int)P.ch, 1), H);
-    int x0 = min(max((int)P.x0, 0), W - cw), y0 = min(max((int)P.y0, 0), H - ch);
+    int cw = min(max((int)p[2], 1), W), ch = min(max((int)p[3], 1), H);
+    int x0 = min(max((int)p[0], 0), W - cw), y0 = min(max((int)p[1], 0), H - ch);
     int* kx = reinterpret_cast<int*>(lds);               // [S][T]
     int* ky = kx + S * T;                                // [S][T]
     int* xmin_x = ky + S * T;                            // [S] each
@@ -179,7 +196,8 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
     __syncthreads();
     const unsigned char* img = src + (long long)b * H * W * 3;
     float* o = out + (long long)b * 3 * S * S;
-    const bool flip = P.flip > 0.5f;
+    const bool flip = p[8] > 0.5f;
+    const bool vflip = EX && p[9] > 0.5f;
     for (int c = 0; c < 3; ++c) {
         for (int i = t; i < ch * S; i += nt) {           // horizontal pass over the rows of the crop
             const int y = i / S, ox = i - y * S;
@@ -196,33 +214,73 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
             const unsigned char* col = tmp + ymin_y[oy] * S + ox;
             int ss = 1 << (kResampleBits - 1);
             for (int y = 0; y < cnt_y[oy]; ++y) ss += (int)col[y * S] * k[y];
-            o[c * S * S + oy * S + (flip ? S - 1 - ox : ox)] = (float)clip8(ss);
+            o[c * S * S + (vflip ? S - 1 - oy : oy) * S + (flip ? S - 1 - ox : ox)] = (float)clip8(ss);
         }
         __syncthreads();
     }
-    const int* perm = kPerm[min(max((int)P.order, 0), 5)];
-    const int contrast_pos = perm[0] == 1 ? 0 : (perm[1] == 1 ? 1 : 2);
-    // mean of the L image as the contrast step meets it: int(ImageStat.Stat(L).mean[0] + 0.5)
-    long long part = 0;
-    for (int i = t; i < S * S; i += nt) {
-        int v[3] = {(int)o[i], (int)o[S * S + i], (int)o[2 * S * S + i]};
-        for (int k = 0; k < contrast_pos; ++k) apply_op(perm[k], P, 0, v);
-        part += pil_luma(v[0], v[1], v[2]);
+    Jitter J;
+    J.b = p[4]; J.c = p[5]; J.s = p[6];
+    J.shift = 0;
+    J.n = 3;
+    if (!EX || (int)p[13] == 0) {                        // the 12-float rule: all three ops in the order of the code 0..5
+        const int* perm = kPerm[min(max((int)p[7], 0), 5)];
+        J.seq = perm[0] | (perm[1] << 2) | (perm[2] << 4);
+    } else {
+        J.n = min(max((int)p[13], 0), 4);
+        J.seq = 0;
+        for (int k = 0; k < J.n; ++k) J.seq |= ((int)p[14 + k] & 3) << (2 * k);
     }
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-    if ((t & 63) == 0) red[t >> 6] = part;
-    __syncthreads();
-    long long tot = 0;
-    for (int w = 0; w < (nt >> 6); ++w) tot += red[w];
-    const int mean_l = (int)((double)tot / (double)(S * S) + 0.5);
+    bool gray = false;
+    int nbox = 0;
+    int box[4][4];                                       // top, left, height, width
+    if (EX) {
+        J.shift = (int)((double)p[10] * 255.0) & 255;    // np.int32(hue_factor * 255).astype(np.uint8)
+        if (p[12] > 0.5f) J.n = 0;                       // RandomApply left the jitter out
+        gray = p[11] > 0.5f;
+        nbox = min(max((int)p[18], 0), 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) box[k][q] = k < nbox ? (int)p[20 + 4 * k + q] : 0;
+    }
+    int contrast_pos = -1;
+    for (int k = J.n - 1; k >= 0; --k)
+        if (((J.seq >> (2 * k)) & 3) == kOpContrast) contrast_pos = k;
+    // mean of the L image as the contrast step meets it: int(ImageStat.Stat(L).mean[0] + 0.5)
+    int mean_l = 0;
+    if (!EX || contrast_pos >= 0) {
+        long long part = 0;
+        for (int i = t; i < S * S; i += nt) {
+            int v[3] = {(int)o[i], (int)o[S * S + i], (int)o[2 * S * S + i]};
+            apply_seq<EX>(J, contrast_pos, 0, v);
+            part += pil_luma(v[0], v[1], v[2]);
+        }
+        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+        if ((t & 63) == 0) red[t >> 6] = part;
+        __syncthreads();
+        long long tot = 0;
+        for (int w = 0; w < (nt >> 6); ++w) tot += red[w];
+        mean_l = (int)((double)tot / (double)(S * S) + 0.5);
+    }
     for (int i = t; i < S * S; i += nt) {
         int v[3] = {(int)o[i], (int)o[S * S + i], (int)o[2 * S * S + i]};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) apply_op(perm[k], P, mean_l, v);
+        apply_seq<EX>(J, J.n, mean_l, v);
+        if (EX && gray) v[0] = v[1] = v[2] = pil_luma(v[0], v[1], v[2]);      // RandomGrayscale: convert("L") in three channels
         // ToTensor (uint8 / 255) then Normalize ((x - mean) / std), float32 like torchvision
-        o[i] = ((float)v[0] / 255.0f - m0) / s0;
-        o[S * S + i] = ((float)v[1] / 255.0f - m1) / s1;
-        o[2 * S * S + i] = ((float)v[2] / 255.0f - m2) / s2;
+        float r0 = ((float)v[0] / 255.0f - m0) / s0;
+        float r1 = ((float)v[1] / 255.0f - m1) / s1;
+        float r2 = ((float)v[2] / 255.0f - m2) / s2;
+        if (EX && nbox > 0) {                            // RandomErasing (mode "const") on the normalised tensor
+            const int y = i / S, x = i - y * S;
+            bool hit = false;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                hit |= k < nbox && y >= box[k][0] && y < box[k][0] + box[k][2] && x >= box[k][1] && x < box[k][1] + box[k][3];
+            if (hit) r0 = r1 = r2 = 0.0f;
+        }
+        o[i] = r0;
+        o[S * S + i] = r1;
+        o[2 * S * S + i] = r2;
     }
 }
 
@@ -238,26 +296,137 @@ extern "C" int sc_knn_alpha(const float* xy, int N, int K, int mode, float sigma
     return 0;
 }
 
-extern "C" int sc_augment_tiles(const void* src_u8_hwc, int B, int H, int W, const float* params12, float* out_nchw,
-                                int S, const float* mean3_host, const float* std3_host, void* stream) {
-    SC_CHECK(B >= 1 && H >= 1 && W >= 1 && S >= 1, "sc_augment_tiles: bad shape B=%d H=%d W=%d S=%d", B, H, W, S);
-    SC_CHECK(mean3_host && std3_host && std3_host[0] > 0 && std3_host[1] > 0 && std3_host[2] > 0,
-             "sc_augment_tiles: mean / std (host pointers to 3 floats) required");
+namespace {
+
+// shape checks, filter taps and LDS bytes shared by both augmentation entries; 0 or an error code
+int augment_plan(const char* who, int B, int H, int W, int S, const float* mean3, const float* std3, int& T, size_t& lds) {
+    SC_CHECK(B >= 1 && H >= 1 && W >= 1 && S >= 1, "%s: bad shape B=%d H=%d W=%d S=%d", who, B, H, W, S);
+    SC_CHECK(mean3 && std3 && std3[0] > 0 && std3[1] > 0 && std3[2] > 0, "%s: mean / std (host pointers to 3 floats) required",
+             who);
     // taps per output position: support 2 * max(scale, 1) either side of the centre, worst case = the whole tile
     const double fs = fmax(1.0, fmax((double)W, (double)H) / (double)S);
-    const int T = (int)(4.0 * fs + 0.5) + 2;
-    SC_CHECK(T <= 64, "sc_augment_tiles: downsampling %dx%d tiles to %d needs %d filter taps (> 64)", W, H, S, T);
-    const size_t lds = (size_t)(2 * S * T + 4 * S) * sizeof(int) + (size_t)H * S;
-    SC_CHECK(lds <= 160 * 1024 - 256, "sc_augment_tiles: %d x %d tiles at output size %d need %zu bytes of LDS", H, W, S, lds);
+    T = (int)(4.0 * fs + 0.5) + 2;
+    SC_CHECK(T <= 64, "%s: downsampling %dx%d tiles to %d needs %d filter taps (> 64)", who, W, H, S, T);
+    lds = (size_t)(2 * S * T + 4 * S) * sizeof(int) + (size_t)H * S;
+    SC_CHECK(lds <= 160 * 1024 - 256, "%s: %d x %d tiles at output size %d need %zu bytes of LDS", who, H, W, S, lds);
+    return 0;
+}
+
+template <bool EX>
+void augment_launch(const void* src, int B, int H, int W, const float* params_dev, int stride, float* out, int S, int T,
+                    size_t lds, const float* mean3, const float* std3, hipStream_t stream) {
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&augment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&augment_kernel<EX>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024 - 256);
         attr_done = true;
     }
-    augment_kernel<<<B, 1024, lds, (hipStream_t)stream>>>((const unsigned char*)src_u8_hwc, H, W, params12, out_nchw, S, T,
-                                                          mean3_host[0], mean3_host[1], mean3_host[2], std3_host[0],
-                                                          std3_host[1], std3_host[2]);
+    augment_kernel<EX><<<B, 1024, lds, stream>>>((const unsigned char*)src, H, W, params_dev, stride, out, S, T, mean3[0],
+                                                 mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+}
+
+bool is_int_in(float v, int lo, int hi) { return v >= (float)lo && v <= (float)hi && v == (float)(int)v; }
+
+// One extended row: 0, or an error code with sc_last_error set.  `uses_ex` reports whether the row asks for anything the
+// 12-float kernel cannot do.
+int augment_check_row(const float* p, int b, int S, bool& uses_ex) {
+    SC_CHECK(is_int_in(p[13], 0, 4), "sc_augment_tiles_ex: row %d: %g jitter ops (0 = the 12-float rule, else 1..4)", b, p[13]);
+    const int n = (int)p[13];
+    int seen = 0;
+    bool hue = false;
+    for (int k = 0; k < n; ++k) {
+        SC_CHECK(is_int_in(p[14 + k], 0, 3), "sc_augment_tiles_ex: row %d: op code %g at position %d is out of range 0..3", b,
+                 p[14 + k], k);
+        const int op = (int)p[14 + k];
+        SC_CHECK(!(seen >> op & 1), "sc_augment_tiles_ex: row %d: op %d appears twice in the jitter sequence", b, op);
+        seen |= 1 << op;
+        hue |= op == kOpHue;
+    }
+    SC_CHECK(p[10] >= -0.5f && p[10] <= 0.5f, "sc_augment_tiles_ex: row %d: hue factor %g outside [-0.5, 0.5]", b, p[10]);
+    SC_CHECK(is_int_in(p[18], 0, 4), "sc_augment_tiles_ex: row %d: %g erase boxes (at most 4)", b, p[18]);
+    const int nbox = (int)p[18];
+    for (int k = 0; k < nbox; ++k) {
+        const float* q = p + 20 + 4 * k;
+        SC_CHECK(is_int_in(q[0], 0, S - 1) && is_int_in(q[1], 0, S - 1) && is_int_in(q[2], 1, S) && is_int_in(q[3], 1, S) &&
+                     (int)q[0] + (int)q[2] <= S && (int)q[1] + (int)q[3] <= S,
+                 "sc_augment_tiles_ex: row %d: erase box %d (top %g, left %g, height %g, width %g) is not inside the %d x %d output",
+                 b, k, q[0], q[1], q[2], q[3], S, S);
+    }
+    uses_ex = n != 0 || p[9] > 0.5f || p[11] > 0.5f || p[12] > 0.5f || nbox > 0;
+    return 0;
+}
+
+// Parameter rows of sc_augment_tiles_ex travel host -> pinned slot -> device slot on the caller's stream.  A slot is taken
+// again only after the kernel that last read it has finished (its event), so the call never waits for the stream it feeds.
+struct ParamSlot {
+    float* host = nullptr;
+    float* dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool busy = false;
+};
+constexpr int kParamSlots = 4;
+ParamSlot g_slots[kParamSlots];
+int g_next_slot = 0;
+std::mutex g_slot_mu;
+
+}  // namespace
+
+extern "C" int sc_augment_tiles(const void* src_u8_hwc, int B, int H, int W, const float* params12, float* out_nchw,
+                                int S, const float* mean3_host, const float* std3_host, void* stream) {
+    int T;
+    size_t lds;
+    if (int rc = augment_plan("sc_augment_tiles", B, H, W, S, mean3_host, std3_host, T, lds)) return rc;
+    augment_launch<false>(src_u8_hwc, B, H, W, params12, 12, out_nchw, S, T, lds, mean3_host, std3_host, (hipStream_t)stream);
     SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_augment_tiles_ex(const void* src_u8_hwc, int B, int H, int W, const float* params_host, int param_stride,
+                                   float* out_nchw, int S, const float* mean3_host, const float* std3_host, void* stream) {
+    int T;
+    size_t lds;
+    if (int rc = augment_plan("sc_augment_tiles_ex", B, H, W, S, mean3_host, std3_host, T, lds)) return rc;
+    SC_CHECK(params_host && param_stride >= kAugRow, "sc_augment_tiles_ex: params (HOST pointer) with a row stride >= %d floats",
+             kAugRow);
+    bool any_ex = false;
+    for (int b = 0; b < B; ++b) {
+        bool uses_ex = false;
+        if (int rc = augment_check_row(params_host + (long long)b * param_stride, b, S, uses_ex)) return rc;
+        any_ex |= uses_ex;
+    }
+    std::lock_guard<std::mutex> lock(g_slot_mu);
+    ParamSlot& slot = g_slots[g_next_slot];
+    g_next_slot = (g_next_slot + 1) % kParamSlots;
+    if (slot.busy) {
+        SC_CHECK(hipEventSynchronize(slot.done) == hipSuccess, "sc_augment_tiles_ex: waiting for a parameter slot failed");
+        slot.busy = false;
+    }
+    const size_t bytes = (size_t)B * kAugRow * sizeof(float);
+    if (slot.cap < bytes) {
+        if (slot.host) (void)hipHostFree(slot.host);
+        if (slot.dev) (void)hipFree(slot.dev);
+        slot.host = slot.dev = nullptr;
+        slot.cap = 0;
+        const size_t cap = bytes + bytes / 4;
+        SC_CHECK(hipHostMalloc(reinterpret_cast<void**>(&slot.host), cap, hipHostMallocDefault) == hipSuccess &&
+                     hipMalloc(reinterpret_cast<void**>(&slot.dev), cap) == hipSuccess,
+                 "sc_augment_tiles_ex: no memory for %zu bytes of parameter rows", cap);
+        slot.cap = cap;
+    }
+    if (!slot.done)
+        SC_CHECK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming) == hipSuccess,
+                 "sc_augment_tiles_ex: hipEventCreate failed");
+    for (int b = 0; b < B; ++b)
+        memcpy(slot.host + (size_t)b * kAugRow, params_host + (long long)b * param_stride, kAugRow * sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    SC_CHECK(hipMemcpyAsync(slot.dev, slot.host, bytes, hipMemcpyHostToDevice, st) == hipSuccess,
+             "sc_augment_tiles_ex: copying the parameter rows failed");
+    // rows that use nothing beyond the 12-float set run the 12-float kernel (same bytes, no extended-row reads)
+    if (any_ex) augment_launch<true>(src_u8_hwc, B, H, W, slot.dev, kAugRow, out_nchw, S, T, lds, mean3_host, std3_host, st);
+    else augment_launch<false>(src_u8_hwc, B, H, W, slot.dev, kAugRow, out_nchw, S, T, lds, mean3_host, std3_host, st);
+    SC_LAUNCH_CHECK();
+    slot.busy = hipEventRecord(slot.done, st) == hipSuccess;
+    if (!slot.busy) (void)hipStreamSynchronize(st);
     return 0;
 }

@@ -792,6 +792,34 @@ def augment_tiles(src_u8: torch.Tensor, params: torch.Tensor, out_size: int, mea
     return out
 
 
+AUG_ROW = 36      # SC_AUG_ROW of include/spatial_clip_hip.h
+
+
+def augment_tiles_ex(src_u8: torch.Tensor, params: torch.Tensor, out_size: int, mean, std,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B,H,W,3] + HOST params fp32 [B, stride >= AUG_ROW] -> normalised fp32 [B,3,S,S]: ``augment_tiles`` plus vertical
+    flip, hue, the jitter switch, grayscale and erase boxes (row layout: include/spatial_clip_hip.h).  The rows stay on the
+    host: the entry checks them and copies them to the device on the current stream itself."""
+    if not src_u8.is_cuda or src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3 \
+            or not src_u8.is_contiguous():
+        raise TypeError("augment_tiles_ex: src must be a contiguous device uint8 [B,H,W,3] tensor")
+    B, H, W, _ = src_u8.shape
+    if params.is_cuda or params.dtype != torch.float32 or params.dim() != 2 or params.shape[0] != B \
+            or params.shape[1] < AUG_ROW or not params.is_contiguous():
+        raise ValueError(f"augment_tiles_ex: params must be a contiguous host fp32 [B, >= {AUG_ROW}] tensor")
+    if out is None:
+        out = torch.empty((B, 3, out_size, out_size), dtype=torch.float32, device=src_u8.device)
+    elif tuple(out.shape) != (B, 3, out_size, out_size) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != src_u8.device:
+        raise ValueError("augment_tiles_ex: out must be a contiguous fp32 [B,3,S,S] tensor on the source's device")
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    check(_lib.lib().sc_augment_tiles_ex(src_u8.data_ptr(), B, H, W, params.data_ptr(), int(params.shape[1]), out.data_ptr(),
+                                         out_size, ctypes.cast(m3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p),
+                                         _stream()), "sc_augment_tiles_ex")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ fp8 forward path
 def quantize_rows_fp8_batched(desc: torch.Tensor, block_prefix: torch.Tensor, n: int, total_blocks: int) -> None:
     """Row-wise e4m3 copies of ``n`` matrices in one launch (params.ParamStore._q8_plan builds the device tables)."""

@@ -9,7 +9,9 @@ What runs where
           a rank-weighted gene vector for the gene towers), the random draws of the augmentation parameters
   device  K-nearest-neighbour search per slide and the loss weights alpha (``sc_knn_alpha``), RandomResizedCrop +
           PIL-exact antialiased bicubic resize + flip + 8-bit ColorJitter + Normalize of the whole batch in one launch
-          (``sc_augment_tiles``; byte-identical to the PIL pipeline the reference runs, tests/golden/augment_pil.npz)
+          (``sc_augment_tiles``; byte-identical to the PIL pipeline the reference runs, tests/golden/augment_pil.npz);
+          the loader calls ``sc_augment_tiles_ex``, which adds the rest of ``AugmentationCfg`` in timm's order: vertical
+          flip, hue, ``color_jitter_prob``, grayscale, random erasing (tests/golden/augment_ex_pil.npz)
 The batch dict is the reference's ``_collate_fn`` contract (src/data/spatial_datamodule.py:110-137): ``images``,
 ``texts``, ``image_tile_ids`` = ``text_tile_ids``, ``neighbor_tile_ids`` (pad -1), ``neighbor_alphas`` (pad 0), ``raw_text``.
 Tile ids are global int64 row indices over (sorted slide ids, member order) like the reference's
@@ -190,8 +192,8 @@ def draw_aug_params(B: int, H: int, W: int, aug_cfg: Optional[Dict[str, Any]], r
                     train: bool = True) -> torch.Tensor:
     """One parameter row per sample for ``sc_augment_tiles``.  Training: torchvision RandomResizedCrop semantics
     (area fraction ~ U(scale), log-uniform aspect ratio, 10 attempts then centre crop) and ColorJitter factors
-    ~ U(1 - j, 1 + j) in a random order (timm's ``color_jitter`` scalar -> brightness = contrast = saturation = j, no
-    hue).  Evaluation: the full tile, no jitter."""
+    ~ U(1 - j, 1 + j) in a random order (timm's ``color_jitter`` scalar -> brightness = contrast = saturation = j; hue and
+    the tuple forms, vertical flip, grayscale and erasing: ``draw_aug_params_ex``).  Evaluation: the full tile, no jitter."""
     P = np.zeros((B, 12), dtype=np.float32)
     P[:, 4:7] = 1.0
     P[:, 2], P[:, 3] = W, H
@@ -222,6 +224,135 @@ def draw_aug_params(B: int, H: int, W: int, aug_cfg: Optional[Dict[str, Any]], r
         if j > 0:
             P[b, 4:7] = rng.uniform(max(0.0, 1 - j), 1 + j, size=3)
             P[b, 7] = float(rng.integers(0, 6))
+    return torch.from_numpy(P)
+
+
+AUG_ROW = ops.AUG_ROW          # floats per row of ``sc_augment_tiles_ex`` (include/spatial_clip_hip.h: SC_AUG_ROW)
+_AUG_OPS = ("brightness", "contrast", "saturation", "hue")      # op codes 0..3 of the jitter sequence
+
+
+def parse_aug_cfg(aug_cfg: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """The augmentation settings the device path honours, checked: open_clip's ``AugmentationCfg`` fields (``scale``,
+    ``ratio``, ``color_jitter``, ``color_jitter_prob``, ``gray_scale_prob``, ``re_prob``, ``re_count``, ``use_timm``) and the
+    timm ``create_transform`` kwargs ``hflip``, ``vflip``, ``grayscale_prob``, ``re_mode``.  ``color_jitter``: a scalar j
+    is (j, j, j) without hue (timm), a 3-tuple is (brightness, contrast, saturation), a 4-tuple adds hue.  Raises
+    ``ValueError`` for what the device path cannot do or what torchvision / timm would reject."""
+    cfg = dict(aug_cfg or {})
+
+    def prob(key, default=0.0):
+        v = cfg.get(key)
+        v = default if v is None else float(v)
+        if not 0.0 <= v <= 1.0:
+            raise ValueError(f"aug_cfg.{key} = {v}: a probability in [0, 1]")
+        return v
+
+    for key in ("auto_augment", "gaussian_blur_prob"):
+        if cfg.get(key) is not None:
+            raise ValueError(f"aug_cfg.{key} = {cfg[key]!r}: not available on the device augmentation path "
+                             "(sc_augment_tiles_ex); leave it null")
+    if cfg.get("re_mode", "const") != "const":
+        raise ValueError(f"aug_cfg.re_mode = {cfg['re_mode']!r}: the device path erases with mode 'const' (zeros) only")
+    j = cfg.get("color_jitter", 0.0) or 0.0
+    legacy_jitter = not isinstance(j, (list, tuple))
+    if legacy_jitter:
+        jit = (float(j),) * 3 + (0.0,)
+    elif len(j) in (3, 4):
+        jit = tuple(float(v) for v in j) + (0.0,) * (4 - len(j))
+    else:
+        raise ValueError(f"aug_cfg.color_jitter = {j!r}: a scalar, (brightness, contrast, saturation) or "
+                         "(brightness, contrast, saturation, hue)")
+    if min(jit[:3]) < 0:
+        raise ValueError(f"aug_cfg.color_jitter = {j!r}: brightness / contrast / saturation must not be negative")
+    if not 0.0 <= jit[3] <= 0.5:
+        raise ValueError(f"aug_cfg.color_jitter hue = {jit[3]}: torchvision takes 0 <= hue <= 0.5")
+    gray_keys = [k for k in ("gray_scale_prob", "grayscale_prob") if cfg.get(k) is not None]
+    if len(gray_keys) == 2 and float(cfg["gray_scale_prob"]) != float(cfg["grayscale_prob"]):
+        raise ValueError("aug_cfg.gray_scale_prob and aug_cfg.grayscale_prob are synonyms and disagree")
+    re_count = cfg.get("re_count")
+    re_count = 1 if re_count is None else re_count
+    if int(re_count) != re_count or not 1 <= int(re_count) <= 4:
+        raise ValueError(f"aug_cfg.re_count = {re_count!r}: 1..4 boxes on the device path")
+    return {
+        "scale": tuple(cfg.get("scale", (0.9, 1.0))), "ratio": tuple(cfg.get("ratio", (0.75, 1.3333))),
+        "jitter": jit, "legacy_jitter": legacy_jitter,
+        # timm's create_transform flips with its default hflip = 0.5 (the reference passes no hflip, transform.py:186-204);
+        # the torchvision fallback branch (use_timm false) has no flip
+        "hflip": prob("hflip", 0.5 if cfg.get("use_timm") else 0.0), "vflip": prob("vflip"),
+        "jitter_prob": None if cfg.get("color_jitter_prob") is None else prob("color_jitter_prob"),
+        "gray": prob(gray_keys[0]) if gray_keys else 0.0,
+        "re_prob": prob("re_prob"), "re_count": int(re_count),
+    }
+
+
+def draw_aug_params_ex(B: int, H: int, W: int, aug_cfg: Optional[Dict[str, Any]], rng: np.random.Generator,
+                       train: bool = True, out_size: Optional[int] = None) -> torch.Tensor:
+    """One HOST parameter row of ``AUG_ROW`` floats per sample for ``sc_augment_tiles_ex``, in timm's order: crop, horizontal
+    flip, vertical flip, ColorJitter inside ``RandomApply(p=color_jitter_prob)`` (factors ~ U(max(0, 1 - x), 1 + x), hue
+    ~ U(-h, h), the ops with a non-zero range in a random order), RandomGrayscale, RandomErasing (``re_count`` boxes in the
+    ``out_size`` output, timm's 10 attempts per box: area fraction ~ U(0.02, 1/3) / count, log-uniform aspect in
+    [0.3, 1/0.3]).  Columns 0..11 of a config that uses only ``scale`` / ``ratio`` / scalar ``color_jitter`` / ``hflip`` /
+    ``use_timm`` equal ``draw_aug_params`` from the same generator state bit for bit, the rest is 0; a feature that is
+    off draws nothing.  Evaluation: the full tile, nothing else."""
+    P = np.zeros((B, AUG_ROW), dtype=np.float32)
+    P[:, 4:7] = 1.0
+    P[:, 2], P[:, 3] = W, H
+    if not train or not aug_cfg:
+        return torch.from_numpy(P)
+    c = parse_aug_cfg(aug_cfg)
+    scale, ratio, jit = c["scale"], c["ratio"], c["jitter"]
+    present = [k for k in range(4) if jit[k] > 0]
+    S = int(out_size) if out_size is not None else 0
+    if c["re_prob"] > 0 and S < 1:
+        raise ValueError("draw_aug_params_ex: re_prob > 0 needs out_size (the boxes live in the output)")
+    for b in range(B):
+        cw, ch, x0, y0 = W, H, 0.0, 0.0
+        for _ in range(10):
+            area = H * W * rng.uniform(*scale)
+            ar = math.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1])))
+            w_, h_ = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+            if 0 < w_ <= W and 0 < h_ <= H:
+                cw, ch = w_, h_
+                x0, y0 = float(rng.integers(0, W - w_ + 1)), float(rng.integers(0, H - h_ + 1))
+                break
+        else:
+            x0, y0 = (W - cw) / 2, (H - ch) / 2
+        P[b, 0:4] = (x0, y0, cw, ch)
+        if c["hflip"] > 0:
+            P[b, 8] = float(rng.uniform() < c["hflip"])
+        if c["vflip"] > 0:
+            P[b, 9] = float(rng.uniform() < c["vflip"])
+        if c["jitter_prob"] is not None and present and not rng.uniform() < c["jitter_prob"]:
+            P[b, 12] = 1.0
+        elif c["legacy_jitter"]:
+            if jit[0] > 0:
+                P[b, 4:7] = rng.uniform(max(0.0, 1 - jit[0]), 1 + jit[0], size=3)
+                P[b, 7] = float(rng.integers(0, 6))
+        elif present:
+            for k in present:
+                if k < 3:
+                    P[b, 4 + k] = rng.uniform(max(0.0, 1 - jit[k]), 1 + jit[k])
+                else:
+                    P[b, 10] = rng.uniform(-jit[3], jit[3])
+            P[b, 13] = len(present)
+            P[b, 14:14 + len(present)] = rng.permutation(present)
+        else:
+            P[b, 12] = 1.0
+        if c["gray"] > 0:
+            P[b, 11] = float(rng.uniform() < c["gray"])
+        if c["re_prob"] > 0 and rng.uniform() < c["re_prob"]:
+            n = 0
+            for _ in range(c["re_count"]):
+                for _ in range(10):
+                    area = S * S * rng.uniform(0.02, 1 / 3) / c["re_count"]
+                    ar = math.exp(rng.uniform(math.log(0.3), math.log(1 / 0.3)))
+                    h_, w_ = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+                    if w_ < S and h_ < S:
+                        top, left = int(rng.integers(0, S - h_ + 1)), int(rng.integers(0, S - w_ + 1))
+                        if h_ > 0 and w_ > 0:               # an empty box erases nothing
+                            P[b, 20 + 4 * n:24 + 4 * n] = (top, left, h_, w_)
+                            n += 1
+                        break
+            P[b, 18] = n
     return torch.from_numpy(P)
 
 
@@ -286,13 +417,17 @@ class ShardedSpatialDataModule:
                  dataset_format_kwargs: Optional[Dict[str, Any]] = None, splits: Optional[Dict[str, Any]] = None,
                  image_size: int = 224, n_genes: Optional[int] = None, gene_vocab: Optional[Sequence[str]] = None,
                  aug_cfg: Optional[Dict[str, Any]] = None, alpha_mode: str = "inverse", seed: int = 2025,
-                 centers_per_batch: int = 16, max_neighbors_per_center: int = 4, decode_ahead: int = 8):
+                 centers_per_batch: int = 16, max_neighbors_per_center: int = 4, decode_ahead: int = 8,
+                 steps_per_epoch: Optional[int] = None, val_steps: Optional[int] = None):
+        # steps_per_epoch / val_steps: knobs of the synthetic backend that configs/data/spatial.yaml carries; an epoch here
+        # is one pass over the shards
         if dataset_format != "shards_v1":
             raise ValueError(f"dataset_format {dataset_format!r}: this module reads 'shards_v1' "
                              "(synthetic batches: data.SyntheticSpatialDataModule)")
         self.data_dir, self.k_neighbors, self.batch_size = data_dir, int(k_neighbors), int(batch_size)
         self.splits = dict(splits or {})
         self.image_size, self.aug_cfg, self.alpha_mode, self.seed = int(image_size), aug_cfg, alpha_mode, int(seed)
+        parse_aug_cfg(aug_cfg)          # a setting the device path cannot honour is an error here, not a silent no-op
         self.n_genes = n_genes
         self.gene_to_idx = {g: i for i, g in enumerate(gene_vocab)} if gene_vocab else None
         self.centers_per_batch, self.max_neighbors_per_center = centers_per_batch, max_neighbors_per_center
@@ -432,8 +567,9 @@ class ShardedSpatialDataModule:
                     rows = flat[at:at + len(idx)]
                     tiles = tiles_all[at:at + len(idx)]
                     at += len(idx)
-                    params = draw_aug_params(len(idx), tiles.shape[1], tiles.shape[2], self.aug_cfg, rng, train)
-                    images = ops.augment_tiles(tiles, params.to(dev), self.image_size, OPENAI_MEAN, OPENAI_STD)
+                    params = draw_aug_params_ex(len(idx), tiles.shape[1], tiles.shape[2], self.aug_cfg, rng, train,
+                                                self.image_size)
+                    images = ops.augment_tiles_ex(tiles, params, self.image_size, OPENAI_MEAN, OPENAI_STD)
                     ids = torch.from_numpy(index.tile_ids[np.asarray(idx)])
                     batch = {"images": images, "texts": self._texts_of(st, rows, dev), "image_tile_ids": ids,
                              "text_tile_ids": ids.clone(), "neighbor_tile_ids": st["nbr"][np.asarray(idx)],

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Input pipeline of one batch of 256 tiles (224 x 224 RGB PNG files, tissue-like content): device decode (sc_png_decode) +
-device augmentation (sc_augment_tiles) against PIL decode + the PIL transform on ONE host core."""
+device augmentation (sc_augment_tiles, sc_augment_tiles_ex) against PIL decode + the PIL transform on ONE host core."""
 import io, os, sys, time
 import numpy as np
 import torch
@@ -43,6 +43,14 @@ assert int(status.abs().sum()) == 0
 t_aug = gpu_time(lambda: ops.augment_tiles(tiles, P, S, shards.OPENAI_MEAN, shards.OPENAI_STD))
 t0 = time.time(); blob.cuda(); torch.cuda.synchronize(); t_h2d = (time.time() - t0) * 1e3
 print(f"device: H2D of the compressed batch {t_h2d:.2f} ms, sc_png_decode {t_dec:.2f} ms, sc_augment_tiles {t_aug:.2f} ms per batch of {B}")
+# the extended entry: the same rows zero-extended (they run the 12-float kernel), then every feature of AugmentationCfg on
+FULL = {"scale": [0.9, 1.0], "ratio": [0.75, 1.333], "color_jitter": [0.2, 0.2, 0.2, 0.05], "gray_scale_prob": 0.1,
+        "re_prob": 1.0, "re_count": 4, "use_timm": True, "vflip": 0.5}
+P_legacy = torch.zeros((B, shards.AUG_ROW)); P_legacy[:, :12] = P.cpu()
+P_full = shards.draw_aug_params_ex(B, S, S, FULL, np.random.default_rng(1), out_size=S)
+t_leg = gpu_time(lambda: ops.augment_tiles_ex(tiles, P_legacy, S, shards.OPENAI_MEAN, shards.OPENAI_STD))
+t_full = gpu_time(lambda: ops.augment_tiles_ex(tiles, P_full, S, shards.OPENAI_MEAN, shards.OPENAI_STD))
+print(f"device: sc_augment_tiles_ex {t_leg:.2f} ms on 12-float rows, {t_full:.2f} ms with hue, vertical flip, grayscale and 4 erase boxes on")
 t0 = time.time()
 n_host = 32
 for f in files[:n_host]:
