@@ -327,33 +327,31 @@ class SpatialClipNet(torch.nn.Module):
         backward (True = side stream, False = one stream, None = still measuring, or pinned by SC_OVERLAP=0 / 1)."""
         out = {}
         for name, stack in self._stacks():
-            st = getattr(stack, "_ov_auto", {}).get((getattr(stack, "B", None), getattr(stack, "L", None)))
-            out[name] = None if st is None else st["choice"]
+            out[name] = None if stack.fwd is None else stack.overlap_choice(stack.fwd.B, stack.fwd.L)
         return out
 
     def side_stream_timing(self) -> Dict[str, Optional[Dict[str, float]]]:
         """Per transformer stack: the best backward time (ms) ``SC_OVERLAP=auto`` measured on each schedule, or None."""
         out = {}
         for name, stack in self._stacks():
-            st = getattr(stack, "_ov_auto", {}).get((getattr(stack, "B", None), getattr(stack, "L", None)))
-            out[name] = None if st is None else st.get("ms_best")
+            out[name] = None if stack.fwd is None else stack.overlap_timing(stack.fwd.B, stack.fwd.L)
         return out
 
     def reset_fp8_scaling(self) -> None:
-        """fp8 path: drop the per-tensor scales carried from the previous steps (towers.TransformerStack.reset_fp8_scaling)."""
+        """fp8 path: drop the per-tensor scales carried from the previous steps (stack.Fp8Scales.reset)."""
         for _, stack in self._stacks():
-            stack.reset_fp8_scaling()
+            stack.scales.reset()
 
     def fp8_scaling_state(self) -> Optional[Dict[str, Any]]:
         """Delayed-scaling state of both towers for a checkpoint (None off the fp8 path)."""
         if self.precision != "fp8":
             return None
-        return {name: stack.fp8_scaling_state() for name, stack in self._stacks()}
+        return {name: stack.scales.state() for name, stack in self._stacks()}
 
     def load_fp8_scaling_state(self, state: Optional[Dict[str, Any]]) -> None:
         """Restore what fp8_scaling_state() saved; anything missing or mismatched resets that tower's history instead."""
         for name, stack in self._stacks():
-            stack.load_fp8_scaling_state((state or {}).get(name))
+            stack.scales.load((state or {}).get(name))
 
     def _load_pretrained(self, pretrained: str) -> None:
         if os.path.isfile(pretrained):        # local checkpoint path branch of factory.py:418-421

@@ -1,7 +1,7 @@
 """HIP stream roles of a training step.
 
 The data-gradient chain (forward, dgrad GEMMs, attention / LayerNorm backward, optimiser) is the critical path; the
-weight-gradient GEMMs run on a side stream (towers.TransformerStack.backward).  Running the chain on a HIGH-priority
+weight-gradient GEMMs run on a side stream (stack.SideScheduler).  Running the chain on a HIGH-priority
 stream makes the dispatcher hand free CUs to the chain first, so the side stream only takes what the chain leaves:
 measured +1.1 % pairs/s on ViT-B/16 (one MI355X, interleaved runs).  ``SC_CHAIN_PRIO=0`` keeps the caller's stream.
 """

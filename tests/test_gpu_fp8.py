@@ -458,20 +458,20 @@ def test_fp8_delayed_scaling_state_is_history_checkpointed_and_not_touched_by_ev
     with torch.no_grad():
         f0 = n1(db["images"], db["texts"])["image_features"].clone()
     st = n1.vision.stack
-    assert not st._dq_ready and float(st._dq_amax.abs().max()) == 0.0
+    assert not st.scales.ready and float(st.scales.amax.abs().max()) == 0.0
     for g in opt1.param_groups:
         g["lr"] = g["initial_lr"] = 0.0
     steps(m1, opt1, sch1, 2)
-    assert st._dq_ready and float(st._dq_scale.max()) > 0.0
-    snap = (st._dq_scale.clone(), st._dq_hist.clone(), st._dq_step)
+    assert st.scales.ready and float(st.scales.scale.max()) > 0.0
+    snap = (st.scales.scale.clone(), st.scales.hist.clone(), st.scales.step)
     with torch.no_grad():
         f1 = n1(db["images"], db["texts"])["image_features"]
     assert torch.equal(f0, f1)
-    assert torch.equal(snap[0], st._dq_scale) and torch.equal(snap[1], st._dq_hist) and snap[2] == st._dq_step
-    assert float(st._dq_amax.abs().max()) == 0.0
+    assert torch.equal(snap[0], st.scales.scale) and torch.equal(snap[1], st.scales.hist) and snap[2] == st.scales.step
+    assert float(st.scales.amax.abs().max()) == 0.0
     # (c) replacing the weights forgets the history
     n1.load_state_dict(n1.state_dict())
-    assert not st._dq_ready and float(st._dq_scale.max()) == 0.0 and float(st._dq_hist.max()) == 0.0
+    assert not st.scales.ready and float(st.scales.scale.max()) == 0.0 and float(st.scales.hist.max()) == 0.0
 
     # (d) checkpoint round trip: 5 steps in one go == 3 steps, save, load into a fresh model, 2 more steps
     n2, m2, opt2, sch2 = make()
@@ -544,7 +544,7 @@ def test_e4m3_mlp_weight_gradients_in_the_model(monkeypatch):
             loss = m.training_step(db, step)
             loss.backward()
         torch.cuda.synchronize()
-        used[tag] = n.vision.stack._fwd_w8
+        used[tag] = n.vision.stack.fwd.w8
         grads[tag] = {k: n.store.g(k).detach().cpu().clone() for k in n.state_dict()}
         params = {k: v.cpu() for k, v in n.state_dict().items()}
     assert used["w8"] and not used["ref"]
@@ -625,8 +625,8 @@ def test_e4m3_weight_gradients_do_not_race_the_scale_update_on_the_side_stream(m
             loss.backward()
             torch.cuda.synchronize()
             out.append({k: n.store.g(k).detach().cpu().clone() for k in n.state_dict()})
-            sc.append(n.vision.stack._dq_scale.cpu().clone())
-        assert n.vision.stack._fwd_w8
+            sc.append(n.vision.stack.scales.scale.cpu().clone())
+        assert n.vision.stack.fwd.w8
         runs[ov], scales[ov] = out, sc
     changed = sum(int((scales["1"][i + 1] != scales["1"][i]).sum()) for i in range(1, 4))
     assert changed >= 8, changed                                 # the scales did change between the steps
@@ -649,7 +649,7 @@ def test_encode_image_after_a_training_step_matches_a_fresh_process(tmp_path):
     fresh = net.SpatialClipNet("custom", None, model_cfg=cfg, seed=6, precision="fp8")
     f_img0 = fresh.model.encode_image(batch["images"], normalize=True)
     f_txt0 = fresh.model.encode_text(batch["texts"], normalize=True)
-    assert float(fresh.vision.stack._dq_amax.abs().max()) == 0.0           # an evaluation pass leaves no maxima behind
+    assert float(fresh.vision.stack.scales.amax.abs().max()) == 0.0           # an evaluation pass leaves no maxima behind
     n = net.SpatialClipNet("custom", None, model_cfg=cfg, seed=6, precision="fp8")
     m = module.SpatialClipLitModule(
         n, losses.ClipLoss(local_loss=True, gather_with_grad=True, cache_labels=True),
@@ -663,10 +663,10 @@ def test_encode_image_after_a_training_step_matches_a_fresh_process(tmp_path):
         m.training_step(batch, step).backward()
     torch.cuda.synchronize()
     st = n.vision.stack
-    assert st._dq_ready and st.fp8_train_pass
-    before = (st._dq_scale.clone(), st._dq_amax.clone(), st._dq_hist.clone())
+    assert st.scales.ready and st.fp8_train_pass
+    before = (st.scales.scale.clone(), st.scales.amax.clone(), st.scales.hist.clone())
     f_img1 = n.model.encode_image(batch["images"], normalize=True)
     f_txt1 = n.model.encode_text(batch["texts"], normalize=True)
     assert not st.fp8_train_pass
     assert torch.equal(f_img1, f_img0) and torch.equal(f_txt1, f_txt0)
-    assert all(torch.equal(a, b) for a, b in zip(before, (st._dq_scale, st._dq_amax, st._dq_hist)))
+    assert all(torch.equal(a, b) for a, b in zip(before, (st.scales.scale, st.scales.amax, st.scales.hist)))

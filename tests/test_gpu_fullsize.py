@@ -196,7 +196,7 @@ def test_configs4_vitl14_gene_transformer_full_depth_vs_fp32_oracle(precision):
         oc["lr_scheduler"]["scheduler"].step()
         assert all(torch.equal(before[k], t) for k, t in n.state_dict().items())
         st = n.vision.stack            # (the class-token-only last block has no full-width GELU GEMMs: its two entries stay 0)
-        assert st._dq_ready and float(st._dq_scale[:2 * (st.layers - 1)].min()) > 0.0
+        assert st.scales.ready and float(st.scales.scale[:2 * (st.layers - 1)].min()) > 0.0
         del loss, oc
     with torch.no_grad():
         out = m.model_step({k: v.cuda() for k, v in batch.items()})

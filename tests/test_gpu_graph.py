@@ -139,7 +139,7 @@ def test_towers_side_by_side_give_the_bits_of_the_sequential_order(second, monke
             ls.append(float(loss.detach()))
         n.store.wait_all()
         torch.cuda.synchronize()
-        assert getattr(n.second.stack, "no_side_stream", False) == (mode == "1")
+        assert n.second.stack.no_side_stream == (mode == "1")
         res[mode] = (ls, g0, n.store.master.detach().clone(), opt.exp_avg.clone())
     assert res["0"][0] == res["1"][0]
     for k in (1, 2, 3):
@@ -179,7 +179,7 @@ def test_trainer_fit_with_the_graphed_step_equals_the_enqueued_fit(monkeypatch, 
         gs = tr.graphed_step
         res[mode] = dict(w=n.store.master.detach().clone(), m=tr.optimizer.exp_avg.clone(), hist=[
             {k: v for k, v in h.items() if k != "time_s"} for h in tr.history], replays=0 if gs is None else gs.replays,
-            failed=None if gs is None else gs.failed, side=getattr(n.second.stack, "no_side_stream", False))
+            failed=None if gs is None else gs.failed, side=n.second.stack.no_side_stream)
     assert res["0"]["replays"] == 0 and res["1"]["failed"] is None
     assert res["1"]["replays"] == 2 * 5 - 1          # every full-size batch but the first (it warms the shape); the ragged ones run eagerly
     assert res["0"]["side"] and res["1"]["side"]     # towers side by side in both runs
@@ -202,6 +202,6 @@ def test_train_entry_reference_pairing_vitb32_text_tower(monkeypatch, tmp_path):
     assert net_.cfg.text is not None and net_.cfg.text.vocab_size == 49408 and net_.cfg.vision.patch_size == 32
     gs = objects["trainer"].graphed_step
     assert gs is not None and gs.replays > 0, (gs.failed if gs is not None else None)
-    assert getattr(net_.second.stack, "no_side_stream", False)                              # towers side by side
+    assert net_.second.stack.no_side_stream                              # towers side by side
     assert metrics["train/loss"] == metrics["train/loss"] and "val/loss" in metrics
     assert 0.0 <= metrics["val/R@10"] <= 1.0

@@ -434,8 +434,8 @@ def test_side_stream_auto_selection_keeps_the_bits(monkeypatch):
         for k in g:
             assert torch.equal(g[k], ref[k]), (i, k)
     assert n1.side_stream_choice()["vision"] in (True, False)
-    st = n1.vision.stack._ov_auto[(B, n1.vision.stack.L)]
-    assert len(st["ms"][True]) == 4 and len(st["ms"][False]) == 4 and not st["pending"]
+    st = n1.vision.stack._trials[(B, n1.vision.stack.fwd.L)]
+    assert len(st.ms[True]) == 4 and len(st.ms[False]) == 4 and not st.pending
 
 
 def test_pretrained_file_with_other_grid_is_resized(tmp_path):
@@ -705,7 +705,7 @@ def test_last_block_projects_q_for_the_class_tokens_only(monkeypatch):
         out = m.model_step(db)
         out["loss"].backward()
         torch.cuda.synchronize()
-        assert n.vision.stack._q_cls_only == (mode == "1")
+        assert n.vision.stack.fwd.q_cls_only == (mode == "1")
         res[mode] = (float(out["loss"].detach()), out["image_features"].detach().float().cpu(),
                      {k: n.store.g(k).detach().cpu().double().clone() for k in params})
     assert abs(res["0"][0] - res["1"][0]) < 2e-4 and float((res["0"][1] - res["1"][1]).abs().max()) < 2e-3

@@ -121,7 +121,7 @@ def test_vitb16_full_depth_gradients_vs_fp32_oracle(loss_kind):
         out = m.model_step(db)
         out["loss"].backward()
         torch.cuda.synchronize()
-        assert n.vision.stack._u_holds_grad, "default path must run the stored-gelu' epilogue"
+        assert n.vision.stack.fwd.u_holds_grad, "default path must run the stored-gelu' epilogue"
         med, wmax, worst = stats({k: n.store.g(k).detach().cpu().double() for k in keys})
         dl = abs(float(out["loss"].detach()) - loss32)
         print(f"[full-depth gradients, {loss_kind}, residual stream {stream}] {len(keys)} tensors: relative L2 median {med:.4f}, "

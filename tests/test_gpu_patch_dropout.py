@@ -256,7 +256,7 @@ def test_e4m3_path_drops_patches_within_its_stated_bounds():
         out = m.model_step(db)
         out["loss"].backward()
     torch.cuda.synchronize()
-    assert n.vision.L_run == 9 and n.vision.stack._fwd_w8 and n.patch_dropout_draw == 2
+    assert n.vision.L_run == 9 and n.vision.stack.fwd.w8 and n.patch_dropout_draw == 2
     keep = pd.keep_indices_host(seed, 1, 0, B, 16, 8)
     assert np.array_equal(n.vision.keep_idx.cpu().numpy(), keep)
     p = {k: v.cpu().clone().requires_grad_(True) for k, v in n.state_dict().items()}
