@@ -457,6 +457,22 @@ int sc_adamw_step_dev(float* params, const float* grads, float* exp_avg, float* 
 int sc_grad_sumsq_partial(const float* grads, long long n, double* partial1024, void* stream);
 int sc_grad_norm_final(const double* partial, int n_partial, float grad_scale, float max_norm, float* norm_clip_out,
                        void* stream);
+/* Gradient accumulation over the micro-batches of one optimiser step (Lightning's Trainer(accumulate_grad_batches=N), the
+ * reference's README: `python train.py +trainer.accumulate_grad_batches=10`).  Every backward of this library OVERWRITES the
+ * flat gradient buffer, so the sum lives in a caller-owned fp32 buffer `acc` of the same layout and is folded once per
+ * micro-batch, 12 bytes per parameter:
+ *   mode 0 (first micro-batch)  acc[i]   = scale * grads[i]
+ *   mode 1 (a middle one)       acc[i]   = acc[i] + scale * grads[i]
+ *   mode 2 (the last one)       grads[i] = acc[i] + scale * grads[i]     acc is not written; acc == NULL (a group of one):
+ *                               grads[i] = scale * grads[i]
+ * scale = 1/N (Lightning divides every micro-batch's loss by N, in a short last group too).  Product and sum are two
+ * separately rounded fp32 operations, never an FMA: the bits a CPU gives for `acc + scale * g` in fp32.  In mode 2, with
+ * partial1024 != NULL, the same pass leaves 1024 fp64 partial sums of squares of the NEW grads for sc_grad_norm_final
+ * (n_partial = 1024): fixed summation order, no atomics, bit-reproducible -- a single-process step clips without reading
+ * the gradient a second time.  acc and grads: any 4-byte aligned, non-overlapping device pointers (16-byte aligned pairs
+ * take 16-byte loads and stores).  n == 0 launches nothing (and writes no partials) and returns 0; another mode, a NULL
+ * grads, a NULL acc in modes 0 / 1, or partials in modes 0 / 1 are errors and launch nothing. */
+int sc_grad_accumulate(float* acc, float* grads, long long n, float scale, int mode, double* partial1024, void* stream);
 
 #ifdef __cplusplus
 }

@@ -89,7 +89,128 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---- gradient accumulation (Trainer accumulate_grad_batches): every backward OVERWRITES the flat gradient buffer, so the
+// sum over the micro-batches of a group is a running fp32 buffer beside it, folded once per micro-batch by this kernel:
+//   mode 0 (first)  acc   = scale * grads
+//   mode 1 (add)    acc   = acc + scale * grads
+//   mode 2 (last)   grads = acc + scale * grads   (acc == nullptr: grads = scale * grads), acc untouched
+// 12 bytes per parameter (two reads, one write), nothing else: a streaming kernel.  The product and the sum are two
+// separately rounded fp32 operations, which makes the result bit-for-bit torch's `acc + scale * g` on a CPU.  This library
+// is built with -ffp-contract=fast, under which the backend fuses a multiply into a dependent add whatever the source says
+// (`#pragma clang fp contract(off)` is not enough), so the rounded product passes through an empty asm statement: no
+// instruction, but a value the add cannot be fused across.
+SC_DEVICE float accum_mul(float s, float g) {
+    float p = s * g;
+    asm("" : "+v"(p));
+    return p;
+}
+SC_DEVICE float accum_mul_add(float a, float s, float g) { return a + accum_mul(s, g); }
+
+template <int MODE>
+SC_DEVICE float accum_one(float a, float s, float g, bool has_acc) {
+    if (MODE == 0) return accum_mul(s, g);
+    if (MODE == 2 && !has_acc) return accum_mul(s, g);
+    return accum_mul_add(a, s, g);
+}
+
+// VEC: both pointers 16-byte aligned (every ParamStore range): 16-byte loads and stores, four vectors of each operand in
+// flight per thread, grid-stride.  Otherwise (any 4-byte aligned pair, misaligned alike or differently): one float per
+// lane and trip.  With `partial` (mode 2 only) the same pass leaves the block's fp64 sum of squares of the NEW gradient in
+// partial[blockIdx.x], formed in the fixed order of sumsq_partial_kernel (thread chain, wave butterfly, four waves): no
+// atomics, the same bits from run to run.  The launch then has exactly 1024 blocks, one producer per slot.
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ grads, long long n,
+                                                              float scale, double* __restrict__ partial) {
+    const bool has_acc = acc != nullptr;
+    float* dst = MODE == 2 ? grads : acc;       // one of the operands: every element is read before the same thread writes it
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    double sq = 0.0;
+    if (VEC) {
+        const long long n4 = n >> 2;
+        double s4[4] = {0.0, 0.0, 0.0, 0.0};
+        for (; i + 3 * stride < n4; i += 4 * stride) {
+            f32x4 g[4], a[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                g[u] = reinterpret_cast<const f32x4*>(grads)[i + u * stride];
+                if (MODE != 0 && has_acc) a[u] = reinterpret_cast<const f32x4*>(acc)[i + u * stride];
+                else a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                f32x4 r;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) r[c] = accum_one<MODE>(a[u][c], scale, g[u][c], has_acc);
+                reinterpret_cast<f32x4*>(dst)[i + u * stride] = r;
+                if (MODE == 2 && partial) s4[u] += (double)(r[0] * r[0] + r[1] * r[1]) + (double)(r[2] * r[2] + r[3] * r[3]);
+            }
+        }
+        for (; i < n4; i += stride) {
+            const f32x4 g = reinterpret_cast<const f32x4*>(grads)[i];
+            f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (MODE != 0 && has_acc) a = reinterpret_cast<const f32x4*>(acc)[i];
+            f32x4 r;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r[c] = accum_one<MODE>(a[c], scale, g[c], has_acc);
+            reinterpret_cast<f32x4*>(dst)[i] = r;
+            if (MODE == 2 && partial) sq += (double)(r[0] * r[0] + r[1] * r[1]) + (double)(r[2] * r[2] + r[3] * r[3]);
+        }
+        sq += (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+            for (long long j = n4 << 2; j < n; ++j) {
+                const float r = accum_one<MODE>((MODE != 0 && has_acc) ? acc[j] : 0.f, scale, grads[j], has_acc);
+                dst[j] = r;
+                if (MODE == 2 && partial) sq += (double)r * r;
+            }
+    } else {
+        for (; i < n; i += stride) {
+            const float r = accum_one<MODE>((MODE != 0 && has_acc) ? acc[i] : 0.f, scale, grads[i], has_acc);
+            dst[i] = r;
+            if (MODE == 2 && partial) sq += (double)r * r;
+        }
+    }
+    if (MODE == 2 && partial) {
+        __shared__ double sm[4];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = sq;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+    }
+}
+
+template <int MODE>
+void launch_grad_accumulate(float* acc, float* grads, long long n, float scale, double* partial, hipStream_t st) {
+    const bool vec = ((((uintptr_t)acc) | ((uintptr_t)grads)) & 15) == 0;
+    const long long work = vec ? (n + 3) / 4 : n;
+    long long nb = (work + 255) / 256;
+    if (nb > 1024 || partial != nullptr) nb = 1024;       // the cap of sumsq_partial_kernel; with partials exactly its grid
+    if (vec)
+        grad_accumulate_kernel<MODE, true><<<(int)nb, 256, 0, st>>>(acc, grads, n, scale, partial);
+    else
+        grad_accumulate_kernel<MODE, false><<<(int)nb, 256, 0, st>>>(acc, grads, n, scale, partial);
+}
+
 }  // namespace
+
+extern "C" int sc_grad_accumulate(float* acc, float* grads, long long n, float scale, int mode, double* partial1024,
+                                  void* stream) {
+    SC_CHECK(mode >= 0 && mode <= 2, "sc_grad_accumulate: mode %d (0 = first, 1 = add, 2 = last)", mode);
+    SC_CHECK(grads != nullptr, "sc_grad_accumulate: grads is required");
+    SC_CHECK(n >= 0, "sc_grad_accumulate: n = %lld", n);
+    SC_CHECK(acc != nullptr || mode == 2, "sc_grad_accumulate: mode %d writes acc, which is NULL", mode);
+    SC_CHECK(partial1024 == nullptr || mode == 2, "sc_grad_accumulate: the sums of squares are those of the summed gradient (mode 2)");
+    SC_CHECK(((((uintptr_t)acc) | ((uintptr_t)grads)) & 3) == 0, "sc_grad_accumulate: pointers must be 4-byte aligned");
+    SC_CHECK(acc != grads, "sc_grad_accumulate: acc and grads must not overlap");
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0) launch_grad_accumulate<0>(acc, grads, n, scale, nullptr, st);
+    else if (mode == 1) launch_grad_accumulate<1>(acc, grads, n, scale, nullptr, st);
+    else launch_grad_accumulate<2>(acc, grads, n, scale, partial1024, st);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int sc_grad_norm(const float* grads, long long n, float grad_scale, float max_norm, double* ws,
                             float* norm_clip_out, void* stream) {

@@ -673,6 +673,46 @@ def grad_norm_final(partial, n_partial, grad_scale, max_norm, out2):
     return out2
 
 
+def grad_accumulate(acc, grads, n, scale, mode, partial=None):
+    """One micro-batch folded into the running gradient sum (``sc_grad_accumulate``): mode 0 ``acc = scale * grads``, mode 1
+    ``acc += scale * grads``, mode 2 ``grads = acc + scale * grads`` (``acc=None``: ``grads *= scale``) with, if ``partial``
+    (1024 fp64) is given, the partial sums of squares of the new ``grads`` for ``grad_norm_final``.  Product and sum are rounded
+    separately.  Host tensors evaluate the same expressions with torch (tests of the schedule and of the gloo route; not a
+    product path: no model runs on the host)."""
+    n, mode = int(n), int(mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"grad_accumulate: mode {mode!r}: 0 (first), 1 (add) or 2 (last)")
+    if acc is None and mode != 2:
+        raise ValueError(f"grad_accumulate: mode {mode} writes acc, which is None")
+    if partial is not None and mode != 2:
+        raise ValueError("grad_accumulate: partial sums of squares belong to the summed gradient (mode 2)")
+    for t, name in ((grads, "grads"), (acc, "acc")):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"grad_accumulate: {name}: expected torch.float32, got {t.dtype}")
+        if not t.is_contiguous() or t.numel() < n or n < 0:
+            raise ValueError(f"grad_accumulate: {name} must be contiguous and hold n = {n} floats")
+        if t.device != grads.device:
+            raise ValueError("grad_accumulate: acc and grads live on different devices")
+    if partial is not None and (partial.dtype != torch.float64 or partial.numel() < 1024 or not partial.is_contiguous()
+                                or partial.device != grads.device):
+        raise ValueError("grad_accumulate: partial must be 1024 contiguous float64 on the gradient's device")
+    if not grads.is_cuda:
+        g = grads.view(-1)[:n]
+        prod = g * float(scale)                         # one rounding ...
+        if mode == 2:
+            g.copy_(prod if acc is None else acc.view(-1)[:n] + prod)     # ... and the other
+            if partial is not None:
+                partial[:1024].zero_()
+                partial[0] = g.double().square().sum()
+        else:
+            acc.view(-1)[:n].copy_(prod if mode == 0 else acc.view(-1)[:n] + prod)
+        return
+    check(_lib.lib().sc_grad_accumulate(_ptr(acc), grads.data_ptr(), n, float(scale), mode, _ptr(partial), _stream()),
+          "sc_grad_accumulate")
+
+
 def adamw_step(p, g, m, v, n, lr, beta1, beta2, eps, wd, step, grad_scale, norm_clip, p_bf16=None):
     check(_lib.lib().sc_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(lr), float(beta1),
                                    float(beta2), float(eps), float(wd), int(step), float(grad_scale), _ptr(norm_clip),

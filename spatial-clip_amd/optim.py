@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Iterable, Optional
+from typing import Callable, Iterable, List, Optional, Tuple
 
 import torch
 
@@ -58,6 +58,18 @@ class FusedAdamW:
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self._partials = torch.zeros(1024 * len(exchange.buckets), dtype=torch.float64, device=dev)
+
+    def _clip(self, grad_scale: float, max_norm: Optional[float], sumsq_partial: Optional[torch.Tensor]):
+        """The clip coefficient of the replicated forms (None: no clipping).  ``sumsq_partial``: 1024 fp64 partial sums of squares
+        of the gradient, left by the pass that formed it (``GradAccumulator.fold`` of a group's last micro-batch): the norm is
+        finished from them and the gradient is not read a second time."""
+        if max_norm is None or max_norm <= 0:
+            return None
+        if sumsq_partial is not None:
+            ops.grad_norm_final(sumsq_partial, 1024, grad_scale, max_norm, self.norm_clip)
+        else:
+            ops.grad_norm(self.store.grad, self.store.total, grad_scale, max_norm, self.norm_clip)
+        return self.norm_clip
 
     def _step_sharded(self, grad_scale: float, max_norm: Optional[float]) -> torch.Tensor:
         g = self.param_groups[0]
@@ -108,7 +120,8 @@ class FusedAdamW:
             self._behind = (buckets, order, copies, [st._transpose_plan(cs) for cs in copies])
         return self._behind
 
-    def _step_behind_forward(self, grad_scale: float, max_norm: Optional[float]) -> torch.Tensor:
+    def _step_behind_forward(self, grad_scale: float, max_norm: Optional[float],
+                             sumsq_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The replicated update (one process, or the all-reduce route) bucket by bucket on the communication stream, in the order
         the next forward consumes the buckets: the forward waits per bucket at the first use of its parameters
         (``ParamStore.wait_names``, the mechanism of the sharded optimiser), so all but the first bucket of the HBM-bound update
@@ -118,10 +131,7 @@ class FusedAdamW:
         g = self.param_groups[0]
         st = self.store
         st.wait_all()               # a step without a forward in between: the previous update must be complete
-        clip = None
-        if max_norm is not None and max_norm > 0:
-            ops.grad_norm(st.grad, st.total, grad_scale, max_norm, self.norm_clip)
-            clip = self.norm_clip
+        clip = self._clip(grad_scale, max_norm, sumsq_partial)
         buckets, order, copies, plans = self._behind_plan(int(os.environ.get("SC_ADAMW_BUCKET", 16 * 1024 * 1024)))
         cur = torch.cuda.current_stream(st.device)
         side = streams.comm_stream(st.device)       # (a low-priority stream of its own measured the same on ViT-B/16, worse on ViT-L/14)
@@ -155,7 +165,8 @@ class FusedAdamW:
                                                   self._hyper_host.data_ptr()), "sc_adamw_hyper_host")
         self.hyper.copy_(self._hyper_host, non_blocking=True)
 
-    def step_captured(self, grad_scale: float = 1.0, max_norm: Optional[float] = None) -> torch.Tensor:
+    def step_captured(self, grad_scale: float = 1.0, max_norm: Optional[float] = None,
+                      sumsq_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The replicated one-launch update in the form a hipGraph can replay: clip coefficient and the step-dependent
         scalars from device memory (``refresh_hyper``), no host-side step counter.  Single process only."""
         if self.exchange is not None:
@@ -163,10 +174,7 @@ class FusedAdamW:
         g = self.param_groups[0]
         st = self.store
         st.wait_all()
-        clip = None
-        if max_norm is not None and max_norm > 0:
-            ops.grad_norm(st.grad, st.total, grad_scale, max_norm, self.norm_clip)
-            clip = self.norm_clip
+        clip = self._clip(grad_scale, max_norm, sumsq_partial)
         ops.adamw_step_dev(st.master, st.grad, self.exp_avg, self.exp_avg_sq, st.total, self.hyper, g["betas"][0],
                            g["betas"][1], g["eps"], g["weight_decay"], grad_scale, clip, st.master_bf16)
         st.refresh_compute_copies(mirror_is_fresh=True)
@@ -175,9 +183,15 @@ class FusedAdamW:
     def zero_grad(self, set_to_none: bool = False) -> None:
         """Gradients are overwritten by every backward; nothing to clear."""
 
-    def step(self, grad_scale: float = 1.0, max_norm: Optional[float] = None) -> torch.Tensor:
+    def step(self, grad_scale: float = 1.0, max_norm: Optional[float] = None,
+             sumsq_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``sumsq_partial``: see ``_clip`` (accumulated steps of one process).  The replicated forms take it; the sharded
+        optimiser forms its norm from per-shard partials and refuses it."""
         g = self.param_groups[0]
         st = self.store
+        if self.exchange is not None and sumsq_partial is not None:
+            raise ValueError("FusedAdamW.step: sumsq_partial= is for the replicated optimiser; the sharded exchange "
+                             "(SC_GRAD_EXCHANGE=sharded) computes its own per-shard partials")
         self.step_count += 1
         if self.exchange is not None:
             return self._step_sharded(grad_scale, max_norm)
@@ -186,11 +200,8 @@ class FusedAdamW:
         # longer update and its forward contend for HBM longer than the overlap returns.  SC_ADAMW_BEHIND=1 / 0 forces either form.
         behind = os.environ.get("SC_ADAMW_BEHIND", "auto")
         if st.master.is_cuda and (behind == "1" or (behind not in ("0", "1") and st.total <= 200_000_000)):
-            return self._step_behind_forward(grad_scale, max_norm)
-        clip = None
-        if max_norm is not None and max_norm > 0:
-            ops.grad_norm(st.grad, st.total, grad_scale, max_norm, self.norm_clip)
-            clip = self.norm_clip
+            return self._step_behind_forward(grad_scale, max_norm, sumsq_partial)
+        clip = self._clip(grad_scale, max_norm, sumsq_partial)
         ops.adamw_step(st.master, st.grad, self.exp_avg, self.exp_avg_sq, st.total, g["lr"], g["betas"][0],
                        g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16)
         st.refresh_compute_copies(mirror_is_fresh=True)
@@ -223,6 +234,103 @@ class FusedAdamW:
         else:
             self.exp_avg.copy_(m)
             self.exp_avg_sq.copy_(v)
+
+
+class GradAccumulator:
+    """The running gradient sum of ``Trainer(accumulate_grad_batches=every)``.  Every backward overwrites the flat gradient
+    buffer of the ``ParamStore``, so the sum of a group's micro-batches lives in a second flat fp32 buffer ``acc`` beside it and
+    one streaming kernel (``ops.grad_accumulate``, 12 bytes per parameter) folds each micro-batch in with weight ``1/every``:
+    the first of a group starts the sum, the last leaves ``sum + its own share`` in ``store.grad`` -- where the reducer, the
+    clip and AdamW expect the gradient -- and does not write ``acc``.  ``acc`` is allocated on first use and only when
+    ``every > 1``; no producer kernel learns an accumulate mode."""
+
+    def __init__(self, store, every: int):
+        every = validate_accumulate_grad_batches(every)
+        self.store, self.every = store, every
+        self.scale = 1.0 / every
+        self.acc: Optional[torch.Tensor] = None
+        self.partial: Optional[torch.Tensor] = None     # 1024 fp64 sums of squares of the summed gradient (sumsq_partial())
+        self._folded: List[Tuple[int, int]] = []        # ranges folded since the last hook() (sorted, disjoint)
+
+    def _acc(self) -> torch.Tensor:
+        if self.acc is None:
+            self.acc = torch.zeros(self.store.total, dtype=torch.float32, device=self.store.grad.device)
+        return self.acc
+
+    def sumsq_partial(self) -> torch.Tensor:
+        """The 1024-slot fp64 buffer to pass as ``fold(..., partial=)`` and then as ``FusedAdamW.step(sumsq_partial=)``."""
+        if self.partial is None:
+            self.partial = torch.zeros(1024, dtype=torch.float64, device=self.store.grad.device)
+        return self.partial
+
+    def fold(self, first: bool, last: bool, lo: int = 0, hi: Optional[int] = None, partial: Optional[torch.Tensor] = None) -> None:
+        """Fold ``store.grad[lo:hi]`` of the micro-batch that has just run its backward, on the current stream.  ``first`` /
+        ``last``: its place in the group (both: a group of one, the gradient is only scaled).  ``partial``: whole-buffer folds of
+        a last micro-batch may leave the sums of squares for the clip in it."""
+        hi = self.store.total if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo <= hi <= self.store.total:
+            raise ValueError(f"GradAccumulator.fold: range [{lo}, {hi}) outside the flat buffer of {self.store.total} floats")
+        if partial is not None and (not last or lo != 0 or hi != self.store.total):
+            raise ValueError("GradAccumulator.fold: partial= needs the whole buffer of a group's last micro-batch")
+        if hi == lo:
+            return
+        g = self.store.grad
+        if last:
+            acc = None if first else self._acc()[lo:hi]
+            ops.grad_accumulate(acc, g[lo:hi], hi - lo, self.scale, 2, partial)
+        else:
+            ops.grad_accumulate(self._acc()[lo:hi], g[lo:hi], hi - lo, self.scale, 0 if first else 1)
+
+    def _fold_new(self, first: bool, last: bool, lo: int, hi: int) -> None:
+        """Fold what of [lo, hi) this micro-batch has not folded yet (announced ranges may touch or overlap)."""
+        pos, out = lo, []
+        for a, b in self._folded:
+            if b <= pos or a >= hi:
+                continue
+            if a > pos:
+                out.append((pos, a))
+            pos = max(pos, b)
+        if pos < hi:
+            out.append((pos, hi))
+        for a, b in out:
+            self.fold(first, last, a, b)
+        merged: List[Tuple[int, int]] = []
+        for a, b in sorted(self._folded + out):
+            if merged and a <= merged[-1][1]:
+                merged[-1] = (merged[-1][0], max(merged[-1][1], b))
+            else:
+                merged.append((a, b))
+        self._folded = merged
+
+    def hook(self, first: bool, last: bool, inner: Optional[Callable[[int, int], None]] = None) -> Callable[[int, int], None]:
+        """The ``net.grad_bucket_hook`` of ONE micro-batch: folds each announced range as soon as backward has completed it (on
+        the stream that announces it) and, on a group's last micro-batch only, hands the range on to ``inner``
+        (``reducer.bucket_ready``): the other micro-batches issue no gradient collective (Lightning's ``no_sync``).  Follow the
+        backward with ``fold_rest`` -- before ``reducer.finish()`` -- for what no call announced."""
+        self._folded = []
+
+        def on_range(lo: int, hi: int) -> None:
+            self._fold_new(first, last, int(lo), int(hi))
+            if last and inner is not None:
+                inner(lo, hi)
+        return on_range
+
+    def fold_rest(self, first: bool, last: bool) -> None:
+        """Fold every range of the buffer that the hook of this micro-batch was not called for (``reducer.finish()`` reduces
+        that complement in one go: it has to hold the sum by then)."""
+        self._fold_new(first, last, 0, self.store.total)
+
+
+def validate_accumulate_grad_batches(value) -> int:
+    """``accumulate_grad_batches`` as this build takes it: an integer >= 1 (1: no accumulation).  Lightning also accepts a
+    ``{epoch: N}`` dict through its GradientAccumulationScheduler callback; that form is refused, like every other value."""
+    ok = isinstance(value, int) and not isinstance(value, bool) and value >= 1
+    if not ok:
+        raise ValueError(f"accumulate_grad_batches={value!r}: an integer >= 1 is accepted (1 = an optimiser step after every "
+                         "batch); a per-epoch dict schedule (GradientAccumulationScheduler), 0, negative or fractional "
+                         "values are not")
+    return int(value)
 
 
 def cosine_warmup_lambda(step: int, num_warmup_steps: int, num_training_steps: int, num_cycles: float = 0.5) -> float:

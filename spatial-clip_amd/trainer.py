@@ -1,7 +1,7 @@
 """Minimal Lightning-free trainer honouring the ``lightning.pytorch.Trainer`` kwargs the reference's configs use
 (configs/trainer/*.yaml): max_epochs / max_steps, precision ("bf16-mixed" is what the kernels implement),
-gradient_clip_val, limit_*_batches, fast_dev_run, devices / strategy / num_nodes, default_root_dir,
-enable_checkpointing.
+gradient_clip_val, accumulate_grad_batches, limit_*_batches, fast_dev_run, devices / strategy / num_nodes,
+default_root_dir, enable_checkpointing.
 
 Multi-GPU (reference: ``strategy: ddp``, configs/trainer/ddp.yaml; Lightning re-launches the script per GPU): here
 the launcher is ``python -m torch.distributed.run --nproc-per-node N``; the Trainer joins the RCCL process group the
@@ -9,7 +9,9 @@ launcher describes (``comm.init_from_env``), REFUSES to run when ``devices x num
 the launcher started, and reduces gradients with this package's bucketed all-reduce (no DDPStrategy).
 
 Loop semantics per step: training_step -> loss.backward() -> grad all-reduce (mean) ->
-clip_grad_norm_ -> AdamW.step -> scheduler.step().  Checkpoints (reference: ModelCheckpoint monitor ``val/R@1``,
+clip_grad_norm_ -> AdamW.step -> scheduler.step().  With ``accumulate_grad_batches=N`` the part from the all-reduce on runs
+after every N-th batch and after the epoch's last one, on the sum of the group's gradients, each weighted 1/N
+(``optim.GradAccumulator``; DESIGN.md "Gradient accumulation").  Checkpoints (reference: ModelCheckpoint monitor ``val/R@1``,
 ``save_last``; configs/callbacks/default.yaml:8-14, gated by ``save_ckpt`` -> ``enable_checkpointing``,
 src/train.py:77-99) are written by rank 0 under ``default_root_dir/checkpoints``; ``fit(ckpt_path=...)`` resumes
 weights, optimiser moments, LR schedule and the step counter (src/train.py:119)."""
@@ -17,11 +19,12 @@ from __future__ import annotations
 
 import os
 import time
-from typing import Any, Dict, Optional
+from typing import Any, Dict, List, Optional
 
 import torch
 
 from . import comm, graph, streams
+from .optim import GradAccumulator, validate_accumulate_grad_batches
 
 
 def _to_device(batch: Dict[str, Any], device) -> Dict[str, Any]:
@@ -37,6 +40,28 @@ def _requested_world(devices: Any, num_nodes: int) -> Optional[int]:
     else:
         n = int(devices)
     return n * max(1, int(num_nodes))
+
+
+def accum_steps_after(n_train: int, every: int) -> List[bool]:
+    """Lightning's automatic optimisation: does an optimiser step follow training batch ``i`` (0-based within the epoch, of
+    the ``n_train`` batches left after limit_train_batches / fast_dev_run)?  After every ``every``-th batch and after the
+    epoch's last one -- a short last group still steps."""
+    every = validate_accumulate_grad_batches(every)
+    return [(i + 1) % every == 0 or i == n_train - 1 for i in range(int(n_train))]
+
+
+def steps_per_epoch(n_train: int, every: int) -> int:
+    """Optimiser steps of one epoch of ``n_train`` batches: ceil(n_train / every)."""
+    return -(-int(n_train) // int(every))
+
+
+def resume_position(global_step: int, n_train: int, every: int):
+    """(epoch to continue in, training batches of it to skip) for a checkpoint that counted ``global_step`` optimiser steps.
+    Checkpoints are written at epoch ends and max_steps trips right after an optimiser step, so the count never sits inside a
+    group: the batches already consumed are whole groups."""
+    spe = max(steps_per_epoch(n_train, every), 1)
+    epoch = int(global_step) // spe
+    return epoch, (int(global_step) - epoch * spe) * int(every)
 
 
 class CheckpointCallback:
@@ -61,7 +86,7 @@ class Trainer:
                  limit_train_batches: float = 1.0, limit_val_batches: float = 1.0, limit_test_batches: float = 1.0,
                  deterministic: bool = False, strategy: str = "auto", num_nodes: int = 1, sync_batchnorm: bool = False,
                  default_root_dir: Optional[str] = None, enable_checkpointing: bool = False, callbacks=None, logger=None,
-                 val_check_interval: Any = 1.0, **unused):
+                 val_check_interval: Any = 1.0, accumulate_grad_batches: int = 1, **unused):
         if precision not in ("bf16-mixed", "bf16", "fp8-mixed", "fp8", "32", "32-true", 32):
             raise ValueError(f"precision {precision!r}: 'bf16-mixed' (bf16 MFMA GEMMs, fp32 accumulation / residual stream "
                              "/ master weights) or 'fp8-mixed' (e4m3 MFMA GEMMs in the transformer blocks on the same policy)")
@@ -72,6 +97,13 @@ class Trainer:
             raise RuntimeError("accelerator=cpu: this build has no CPU path (the oracle under oracle/ is test-only)")
         if strategy not in ("auto", "ddp", "ddp_find_unused_parameters_false", "ddp_find_unused_parameters_true", None):
             raise ValueError(f"strategy {strategy!r}: data parallel (one process per GPU, 'ddp') is the only strategy")
+        # Lightning's accumulate_grad_batches (the reference's README: +trainer.accumulate_grad_batches=10): an integer >= 1
+        self.accumulate_grad_batches = validate_accumulate_grad_batches(accumulate_grad_batches)
+        if self.accumulate_grad_batches > 1 and comm.grad_exchange_mode() == "sharded":
+            raise ValueError(f"accumulate_grad_batches={accumulate_grad_batches} with SC_GRAD_EXCHANGE=sharded: the sharded "
+                             "gradient exchange reduce-scatters every backward and has no accumulating form; accepted: "
+                             "accumulate_grad_batches=1 with it, or SC_GRAD_EXCHANGE=allreduce (the default) with any N >= 1")
+        self.accumulator: Optional[GradAccumulator] = None      # built by fit() when accumulate_grad_batches > 1
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.gradient_clip_val = gradient_clip_val
         self.fast_dev_run = fast_dev_run
@@ -165,7 +197,8 @@ class Trainer:
         train = datamodule.train_dataloader()
         n_train = self._limit(len(train), self.limit_train_batches)
         epochs = 1 if self.fast_dev_run else (self.max_epochs or 1)
-        self.estimated_stepping_batches = n_train * epochs if self.max_steps == -1 else self.max_steps
+        every = self.accumulate_grad_batches
+        self.estimated_stepping_batches = steps_per_epoch(n_train, every) * epochs if self.max_steps == -1 else self.max_steps
         model.trainer = self
         net_prec = getattr(model.net, "precision", "bf16")
         if net_prec != self.precision:
@@ -176,7 +209,7 @@ class Trainer:
         opt = cfg["optimizer"]
         sched = cfg.get("lr_scheduler", {}).get("scheduler")
         self.optimizer, self.scheduler = opt, sched
-        start_epoch = 0
+        start_epoch, resume_skip = 0, 0
         rank, W = comm.world()
         # gradient exchange of the group (None without one): the bucketed all-reduce by default, the sharded reduce-scatter /
         # all-gather exchange with SC_GRAD_EXCHANGE=sharded (comm.make_grad_exchange).  Attached before a checkpoint is
@@ -189,14 +222,26 @@ class Trainer:
             if not os.path.isfile(ckpt_path):
                 raise FileNotFoundError(f"ckpt_path {ckpt_path!r} does not exist")
             self.global_step = self.load_checkpoint(ckpt_path, model, opt, sched)
-            start_epoch = self.global_step // max(n_train, 1)
+            start_epoch, resume_skip = resume_position(self.global_step, n_train, every)
         # single process, bf16, FusedAdamW: the step can run as ONE hipGraph (SC_GRAPH=auto: only where the first eager steps
         # show the host as the bottleneck -- the reference's ViT-B-32 / batch-32 experiments; =1 always; =0 never)
+        # (not an accumulated step: its launches differ from micro-batch to micro-batch)
         gstep = None
-        if reducer is None and graph.graph_mode() != "0" and hasattr(opt, "step_captured") and torch.cuda.is_available():
+        if every == 1 and reducer is None and graph.graph_mode() != "0" and hasattr(opt, "step_captured") and torch.cuda.is_available():
             gstep = graph.GraphedTrainStep(model, opt, max_norm=self.gradient_clip_val, grad_scale=1.0 / W,
                                            policy="always" if graph.graph_mode() == "1" else "host_bound")
         self.graphed_step = gstep
+        accum = None
+        if every > 1:
+            # __init__ refused this by the switch's value then; make_grad_exchange read the switch again just now, so what
+            # it built is checked as well: a switch set after construction must not pair a running sum with reduce-scatters
+            if isinstance(reducer, comm.ShardedGradExchange):
+                raise ValueError(f"accumulate_grad_batches={every} with SC_GRAD_EXCHANGE=sharded: not supported (use the "
+                                 "default all-reduce exchange, or accumulate_grad_batches=1)")
+            accum = GradAccumulator(model.net.store, every)
+            clipping = self.gradient_clip_val is not None and self.gradient_clip_val > 0
+        self.accumulator = accum
+        steps_after = accum_steps_after(n_train, every)
         vci = self.val_check_interval
         val_every = 0 if self.fast_dev_run else (int(vci) if isinstance(vci, int) and not isinstance(vci, bool)
                                                  else (max(1, int(n_train * vci)) if vci < 1.0 else 0))
@@ -207,14 +252,37 @@ class Trainer:
                 datamodule.set_epoch(epoch)
             model.train_metrics.reset()
             t0 = time.time()
-            skip = self.global_step - epoch * n_train if epoch == start_epoch else 0     # mid-epoch resume
+            skip = resume_skip if epoch == start_epoch else 0     # mid-epoch resume
             for i, batch in enumerate(train):
                 if i >= n_train or (self.max_steps != -1 and self.global_step >= self.max_steps):
                     break
                 if i < skip:
                     continue
                 batch = _to_device(batch, model.device)
-                if gstep is not None:           # one hipGraph per step where the host is the bottleneck (graph.py); eager otherwise
+                if accum is not None:
+                    # one micro-batch of a group: backward, fold its gradient into the running sum -- on the chain stream, behind
+                    # the joins at the end of backward that opt.step relies on (side-stream weight gradients: SideScheduler.join;
+                    # second tower: net._backward) -- and, behind the group's last one, the step on the summed gradient
+                    first, last = i % every == 0, steps_after[i]
+                    with streams.chain_stream():
+                        if reducer is not None:     # bucket by bucket behind the backward; collectives on the last one only
+                            model.net.grad_bucket_hook = accum.hook(first, last, reducer.bucket_ready)
+                        loss = model.training_step(batch, i)
+                        loss.backward(model.root_gradient(loss))
+                        if reducer is not None:
+                            accum.fold_rest(first, last)
+                            if last:
+                                reducer.finish()
+                                opt.step(grad_scale=1.0 / W, max_norm=self.gradient_clip_val)
+                        else:
+                            partial = accum.sumsq_partial() if last and clipping else None
+                            accum.fold(first, last, partial=partial)
+                            if last:
+                                opt.step(grad_scale=1.0 / W, max_norm=self.gradient_clip_val, sumsq_partial=partial)
+                    if not last:
+                        self._val_in_epoch(model, datamodule, val_every, i, n_train, epoch)
+                        continue
+                elif gstep is not None:         # one hipGraph per step where the host is the bottleneck (graph.py); eager otherwise
                     loss = gstep(batch)
                 else:
                     with streams.chain_stream():
@@ -229,10 +297,7 @@ class Trainer:
                 if self.global_step % self.log_every_n_steps == 0 or self.fast_dev_run:
                     self.history.append({"step": self.global_step,
                                          "train/loss": self._synced(model, "train/loss", float(loss.detach()))})
-                if val_every and (i + 1) % val_every == 0 and (i + 1) < n_train \
-                        and (epoch + 1) % self.check_val_every_n_epoch == 0:
-                    self.history.append({"step": self.global_step, "epoch": epoch, **self._validate(model, datamodule)})
-                    self.val_runs += 1
+                self._val_in_epoch(model, datamodule, val_every, i, n_train, epoch)
             torch.cuda.synchronize()
             rec = {"epoch": epoch, "time_s": time.time() - t0, **model.train_metrics.compute()}
             last_train = next((h["train/loss"] for h in reversed(self.history) if "train/loss" in h), None)
@@ -247,6 +312,13 @@ class Trainer:
                 break
         self.callback_metrics = {k: v for k, v in self.history[-1].items() if isinstance(v, float)} if self.history else {}
         model.net.store.wait_all()      # the last optimiser update may run behind the (absent) next forward: fit returns finished weights
+
+    def _val_in_epoch(self, model, datamodule, val_every: int, i: int, n_train: int, epoch: int) -> None:
+        """val_check_interval inside an epoch: counts TRAINING BATCHES, also under accumulate_grad_batches (as Lightning)."""
+        if val_every and (i + 1) % val_every == 0 and (i + 1) < n_train \
+                and (epoch + 1) % self.check_val_every_n_epoch == 0:
+            self.history.append({"step": self.global_step, "epoch": epoch, **self._validate(model, datamodule)})
+            self.val_runs += 1
 
     # ------------------------------------------------------------------ checkpoints (reference state_dict names)
     def _early_stop(self, rec: Dict[str, Any]) -> bool:
