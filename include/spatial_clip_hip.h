@@ -273,6 +273,26 @@ int sc_embed_ln_bwd_keep(float* dres, const float* patch_out, const float* cls, 
                          const int* slot, const float* mean, const float* rstd, const float* gamma, void* dpatch_bf16,
                          float* dgamma, float* dbeta, float* dpos, float* dcls, float* ws, int B, int L, int n, int d,
                          void* stream);
+/* Stem without LayerNorm (vision_cfg.no_ln_pre, src/open_clip/transformer.py:652): gamma == NULL in any of the eight entry
+ * points above (sc_embed_ln_fwd, _x16, _keep, _keep_x16, sc_embed_ln_bwd, _keep) selects the row kernels' "no LN" body.  beta,
+ * mean, rstd, dgamma, dbeta (and ws) are then ignored, may be NULL and are never written.
+ * Forward: x[b, 0] = cls + pos[0]; x[b, t] = patch_out[...] + pos[row(t)] for t > 0 -- one fp32 add, stored as fp32 or rounded
+ * once to bf16 (_x16).  Backward: d(token) is the incoming dres, left in place untouched; dpatch_bf16 = the bf16 rounding of
+ * its rows t > 0, packed as with LayerNorm; dpos / dcls by the same fixed-order sums (no atomics); no partial dgamma / dbeta
+ * traffic and no finalize launch. */
+
+/* ------------------------------------------------------------------------------------------------ token mean pooling
+ * Average-pooled towers (vision_cfg.pool_type "avg"; VisionTransformer._global_pool, src/open_clip/transformer.py:773-781).
+ * x / dx: contiguous [B, L, d] rows, bf16 or fp32; t0 = first pooled token (1 behind a class token, 0 allowed), n = L - t0 >= 1.
+ * sc_token_pool_fwd: mean[b, c] = (1 / n) * sum_{t >= t0} x[b, t, c], accumulated in fp32 in an order that depends only on
+ * (B, L, t0, d); written as fp32 and / or bf16 (the rounding of the fp32 value), at least one of them.
+ * sc_token_pool_bwd: dx[b, t, c] = 0 for t < t0, d_mean[b, c] / n (fp32 division) for t >= t0; dx_bf16 = round-to-nearest-even
+ * of that fp32 value.  EVERY element of the given outputs is written: nothing has to be zeroed first.
+ * d % 4 == 0, d <= 2048, pointers 16-byte aligned; no atomics, bit-reproducible. */
+int sc_token_pool_fwd(const void* x, int x_is_bf16, int B, int L, int t0, int d, float* mean_f32, void* mean_bf16,
+                      void* stream);
+int sc_token_pool_bwd(const void* d_mean, int d_is_bf16, int B, int L, int t0, int d, float* dx_f32, void* dx_bf16,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------ text tower glue
  * CLIP.encode_text (src/open_clip/model.py:330-345): x = token_embedding[text] + positional_embedding (fp32 residual

@@ -99,8 +99,9 @@ __global__ __launch_bounds__(256) void im2col_strip_kernel(const float* __restri
 // one wave per token row; NV = 16-byte lane slots per row (ceil(d / 256)): a compile-time trip count keeps every load of a
 // row in flight at once (the generic 8-slot loop with run-time predicates ran at 2.5 TB/s, the LayerNorm kernels at 5.7)
 // XB: the residual stream starts in bf16 (x points at bf16 rows): no fp32 copy + cast pass.  Pos: PosFull or PosKeep; token
-// tkn > 0 of sample b reads patch row b * (L - 1) + tkn - 1 in both.
-template <int NV, bool XB, class Pos>
+// tkn > 0 of sample b reads patch row b * (L - 1) + tkn - 1 in both.  LN = false (a tower built with no_ln_pre): the row is the
+// sum itself -- one fp32 add, stored as fp32 or rounded once to bf16; gamma / beta / mean / rstd are never touched.
+template <int NV, bool XB, class Pos, bool LN = true>
 __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restrict__ patch, const float* __restrict__ cls,
                                                            const float* __restrict__ pos, const Pos pos_row,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -122,6 +123,17 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restri
             v[i] = ld4(src + e * 4) + ld4(pr + e * 4);
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
+    }
+    if (!LN) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int e = i * 64 + lane;
+            if (e < nv) {
+                if (XB) stbf4(reinterpret_cast<bf16*>(x) + (long long)row * d + e * 4, v[i]);
+                else st4(x + (long long)row * d + e * 4, v[i]);
+            }
+        }
+        return;
     }
     const float mu = sc_wave_sum(s) / (float)d;
     float q = 0.f;
@@ -150,7 +162,8 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restri
 }
 
 // LN backward of the same rows; every workgroup leaves its partial dgamma / dbeta in partial[blockIdx.x][2][d]
-template <int NV, class Pos>
+// LN = false: d(token) IS the incoming dres, which stays in place untouched; only the packed bf16 d(patch out) is written
+template <int NV, class Pos, bool LN = true>
 __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(float* __restrict__ dres, const float* __restrict__ patch,
                                                            const float* __restrict__ cls, const float* __restrict__ pos,
                                                            const Pos pos_row, const float* __restrict__ mean,
@@ -161,6 +174,26 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(float* __restrict__ d
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // uniform: row pointers in SGPRs
     const int nv = d >> 2;
     const int rows = B * L;
+    if (!LN) {
+        for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+            const int b = row / L, tkn = row - b * L;
+            if (tkn == 0) continue;
+            const float* dr = dres + (long long)row * d;
+            bf16* dp = dpatch + ((long long)b * (L - 1) + (tkn - 1)) * d;
+            f32x4 g[NV];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int e = i * 64 + lane;
+                if (e < nv) g[i] = ld4(dr + e * 4);
+            }
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int e = i * 64 + lane;
+                if (e < nv) stbf4(dp + e * 4, g[i]);
+            }
+        }
+        return;
+    }
     f32x4 ag[NV], ab[NV], gm[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -289,6 +322,8 @@ int embed_ln_fwd_launch(const float* patch_out, const float* cls, const float* p
                         void* stream) {
     embed_nv_dispatch(d, [&](auto NV) {
         auto kernel = xb ? embed_ln_fwd_kernel<NV.value, true, Pos> : embed_ln_fwd_kernel<NV.value, false, Pos>;
+        if (gamma == nullptr)       // no_ln_pre: the "no LN" body
+            kernel = xb ? embed_ln_fwd_kernel<NV.value, true, Pos, false> : embed_ln_fwd_kernel<NV.value, false, Pos, false>;
         kernel<<<(B * L + 3) / 4, 256, 0, (hipStream_t)stream>>>(patch_out, cls, pos, pos_row, gamma, beta, x, mean, rstd, B, L,
                                                                  d, eps);
     }, std::make_integer_sequence<int, MAXV>{});
@@ -302,6 +337,14 @@ int embed_ln_bwd_launch(float* dres, const float* patch_out, const float* cls, c
                         const float* rstd, const float* gamma, void* dpatch_bf16, float* dgamma, float* dbeta, float* ws, int B,
                         int L, int d, hipStream_t st) {
     const int nblk = embed_bwd_blocks(B, L);
+    if (gamma == nullptr) {         // no_ln_pre: no LDS, no partial dgamma / dbeta, no finalize launch
+        embed_nv_dispatch(d, [&](auto NV) {
+            embed_ln_bwd_kernel<NV.value, Pos, false><<<nblk, 256, 0, st>>>(dres, patch_out, cls, pos, pos_row, mean, rstd, gamma,
+                                                                            (bf16*)dpatch_bf16, ws, B, L, d);
+        }, std::make_integer_sequence<int, MAXV>{});
+        SC_LAUNCH_CHECK();
+        return 0;
+    }
     const size_t lds = (size_t)4 * 2 * d * sizeof(float);
     embed_nv_dispatch(d, [&](auto NV) {
         auto kernel = embed_ln_bwd_kernel<NV.value, Pos>;

@@ -18,6 +18,13 @@ class VisionCfg:
     layers: int = 12
     head_width: int = 64
     mlp_ratio: float = 4.0
+    # open_clip vision_cfg.pool_type / no_ln_pre / final_ln_after_pool (src/open_clip/transformer.py:594-603,652,773-823; every
+    # CLIPA config sets avg / true / true): "tok" pools the class token, "avg" the mean of the patch tokens; no_ln_pre drops the
+    # LayerNorm in front of the blocks (and its two parameters); final_ln_after_pool applies ln_post to the pooled row instead of
+    # to every token before the pool.  Keyword-only: positional construction stops at patch_dropout, which stays the last field.
+    pool_type: str = field(default="tok", kw_only=True)
+    no_ln_pre: bool = field(default=False, kw_only=True)
+    final_ln_after_pool: bool = field(default=False, kw_only=True)
     # FLIP patch dropout (open_clip vision_cfg.patch_dropout): fraction of the patch tokens a TRAINING forward drops, 0 = off
     patch_dropout: float = 0.0
 
@@ -42,6 +49,10 @@ class TextCfg:
     heads: int = 8
     layers: int = 12
     mlp_ratio: float = 4.0
+    # open_clip text_cfg.pool_type (text_global_pool, src/open_clip/transformer.py:921-940): the pooled row is the one at
+    # text.argmax(-1) (the EOT token, CLIP's default), the last or the first token; no_causal_mask: full attention (CLIPA)
+    pool_type: str = "argmax"
+    no_causal_mask: bool = False
 
 
 @dataclass
@@ -159,7 +170,8 @@ def check_attention_support(cfg: ModelCfg) -> None:
     attention kernel takes -- raised when the net is constructed, not at its first forward."""
     towers = [("vision", cfg.vision.width, cfg.vision.head_width, cfg.vision.tokens, False)]
     if cfg.text is not None:
-        towers.append(("text", cfg.text.width, cfg.text.width // max(cfg.text.heads, 1), cfg.text.context_length, True))
+        towers.append(("text", cfg.text.width, cfg.text.width // max(cfg.text.heads, 1), cfg.text.context_length,
+                       not cfg.text.no_causal_mask))
     if cfg.gene is not None and cfg.gene.kind == "transformer":
         towers.append(("gene", cfg.gene.width, cfg.gene.head_width, cfg.gene.tokens, False))
     for tower, width, dh, tokens, causal in towers:
@@ -171,6 +183,88 @@ def check_attention_support(cfg: ModelCfg) -> None:
                 f"{tower} tower: no attention kernel for head dim {dh} at {tokens} tokens"
                 f"{' (causal)' if causal else ''}; supported: head dims {' / '.join(map(str, ATTN_HEAD_DIMS))} up to "
                 f"{ATTN_MAX_TOKENS} tokens, and head dim 64 (non-causal) at any length")
+
+
+# open_clip's CLIPVisionCfg / CLIPTextCfg keys (src/open_clip/model.py:28-103) that SpatialClipNet(vision_cfg= / text_cfg=) takes
+VISION_OVERRIDE_KEYS = ("image_size", "patch_size", "width", "layers", "head_width", "mlp_ratio", "patch_dropout", "pool_type",
+                        "no_ln_pre", "final_ln_after_pool")
+TEXT_OVERRIDE_KEYS = ("context_length", "vocab_size", "width", "heads", "layers", "mlp_ratio", "pool_type", "no_causal_mask")
+TEXT_IGNORED_KEYS = ("hf_tokenizer_name", "tokenizer_kwargs")
+VISION_POOL_TYPES = ("tok", "avg")
+TEXT_POOL_TYPES = ("argmax", "last", "first")
+# keys of features this build does not have: accepted only with open_clip's default value
+_VISION_UNSUPPORTED = {"ls_init_value": None, "attentional_pool": False, "attn_pooler_queries": 256, "attn_pooler_heads": 8,
+                       "pos_embed_type": "learnable", "output_tokens": False, "timm_model_name": None,
+                       "timm_model_pretrained": False, "timm_pool": "avg", "timm_proj": "linear", "timm_proj_bias": False,
+                       "timm_drop": 0.0, "timm_drop_path": None}
+_TEXT_UNSUPPORTED = {"ls_init_value": None, "hf_model_name": None, "embed_cls": False, "output_tokens": False,
+                     "pos_embed_type": "learnable", "attentional_pool": False, "attn_pooler_queries": 256,
+                     "attn_pooler_heads": 8}
+
+
+def _check_override_keys(tower: str, over, known, ignored, unsupported) -> Dict[str, object]:
+    if not hasattr(over, "items"):
+        raise TypeError(f"{tower}_cfg must be a mapping of open_clip {tower}_cfg keys, got {type(over)}")
+    out = {}
+    for k, v in over.items():
+        k = str(k)
+        if k in known:
+            out[k] = v
+        elif k in ignored:
+            continue
+        elif k in unsupported or k.startswith(("timm_", "attn_pooler_")):
+            default = unsupported.get(k)
+            same = v == default and type(v) is type(default) if isinstance(default, bool) else v == default
+            if not same:
+                raise ValueError(f"{tower}_cfg key {k!r} = {v!r}: not supported by this build (only open_clip's default "
+                                 f"{default!r} is accepted)")
+        else:
+            raise ValueError(f"{tower}_cfg key {k!r} is not known; accepted: {', '.join(known + ignored)}")
+    return out
+
+
+def _typed(tower: str, key: str, value, like):
+    """The override ``value`` in the type of the field's default ``like`` (a YAML 4 for mlp_ratio becomes 4.0)."""
+    try:
+        if isinstance(like, bool):
+            if not isinstance(value, (bool, int)) or value not in (0, 1, True, False):
+                raise TypeError
+            return bool(value)
+        if isinstance(like, int):
+            if int(value) != value:
+                raise TypeError
+            return int(value)
+        if isinstance(like, float):
+            return float(value)
+        return str(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{tower}_cfg key {key!r}: {value!r} is not a valid {type(like).__name__}") from None
+
+
+def with_vision_overrides(cfg: ModelCfg, over) -> ModelCfg:
+    """A copy of ``cfg`` with the open_clip ``vision_cfg`` mapping ``over`` applied on top of its vision tower.  ValueError,
+    naming the key, for a key of a feature this build lacks (unless it carries open_clip's default) or an unknown key."""
+    vals = _check_override_keys("vision", over, VISION_OVERRIDE_KEYS, (), _VISION_UNSUPPORTED)
+    base = VisionCfg()
+    vals = {k: _typed("vision", k, v, getattr(base, k)) for k, v in vals.items()}
+    if vals.get("pool_type", "tok") not in VISION_POOL_TYPES:
+        raise ValueError(f"vision_cfg key 'pool_type' = {vals['pool_type']!r}: this build pools {' / '.join(VISION_POOL_TYPES)}")
+    vision = replace(cfg.vision, **vals)
+    if vision.image_size <= 0 or vision.patch_size <= 0 or vision.image_size % vision.patch_size:
+        raise ValueError(f"vision_cfg: image_size {vision.image_size} is not a positive multiple of patch_size {vision.patch_size}")
+    return replace(cfg, vision=vision)
+
+
+def with_text_overrides(cfg: ModelCfg, over) -> ModelCfg:
+    """The same for the reference's text tower (``text_cfg``); ValueError on a config without one (``-gene`` / ``-genetr``)."""
+    if cfg.text is None:
+        raise ValueError("text_cfg: this model has no text tower (a -gene / -genetr model fills the text slot with a gene tower)")
+    vals = _check_override_keys("text", over, TEXT_OVERRIDE_KEYS, TEXT_IGNORED_KEYS, _TEXT_UNSUPPORTED)
+    base = TextCfg()
+    vals = {k: _typed("text", k, v, getattr(base, k)) for k, v in vals.items()}
+    if vals.get("pool_type", "argmax") not in TEXT_POOL_TYPES:
+        raise ValueError(f"text_cfg key 'pool_type' = {vals['pool_type']!r}: this build pools {' / '.join(TEXT_POOL_TYPES)}")
+    return replace(cfg, text=replace(cfg.text, **vals))
 
 
 def list_models():

@@ -19,7 +19,8 @@ from typing import Any, Callable, Dict, List, Optional
 import torch
 
 from . import comm, ops, streams
-from .model_configs import ModelCfg, check_attention_support, get_model_config, with_image_size
+from .model_configs import (ModelCfg, check_attention_support, get_model_config, with_image_size, with_text_overrides,
+                            with_vision_overrides)
 from .params import ParamStore
 from .patch_dropout import check_fraction
 from .towers import GeneTower, GeneTransformerTower, TextTower, VisionTower
@@ -220,7 +221,8 @@ class SpatialClipNet(torch.nn.Module):
                  tokenizer_vocab: Optional[str] = None, precision: str = "bf16", grad_checkpointing: bool = False,
                  residual_stream: str = "bf16", init_logit_scale: Optional[float] = None,
                  init_logit_bias: Optional[float] = None, force_image_size: Optional[int] = None,
-                 force_patch_dropout: Optional[float] = None):
+                 force_patch_dropout: Optional[float] = None, vision_cfg: Optional[Any] = None,
+                 text_cfg: Optional[Any] = None):
         super().__init__()
         if force_patch_dropout is not None:
             check_fraction(force_patch_dropout)     # ValueError outside [0, 1), before anything is built
@@ -236,6 +238,16 @@ class SpatialClipNet(torch.nn.Module):
             # open_clip's create_model kwargs (main.py:225-227 for --siglip: log(10) and -10) override the model config
             self.cfg = replace(self.cfg, **{k: float(v) for k, v in (("init_logit_scale", init_logit_scale),
                                                                       ("init_logit_bias", init_logit_bias)) if v is not None})
+        # ``vision_cfg`` / ``text_cfg``: mappings with open_clip's key names (the dicts of an open_clip model JSON as they are),
+        # applied on top of the named or given config BEFORE force_image_size / force_patch_dropout, which keep the last word.
+        # Keys of features this build lacks raise ValueError naming the key (model_configs.with_vision_overrides).
+        self._foreign_tokenizer: Optional[str] = None
+        if vision_cfg is not None:
+            self.cfg = with_vision_overrides(self.cfg, vision_cfg)
+        if text_cfg is not None:
+            self.cfg = with_text_overrides(self.cfg, text_cfg)
+            name = text_cfg.get("hf_tokenizer_name")
+            self._foreign_tokenizer = None if name is None else str(name)
         if force_image_size is not None:
             # open_clip's create_model(force_image_size=...) (src/open_clip/factory.py:438-439): the vision tower's input
             # size, and with it the token count; a checkpoint's positions are resized to it on load
@@ -375,6 +387,11 @@ class SpatialClipNet(torch.nn.Module):
         if self.cfg.gene is not None:
             return torch.as_tensor(x, dtype=torch.float32)
         if isinstance(x, (str, list, tuple)) and (isinstance(x, str) or (len(x) and isinstance(x[0], str))):
+            if self._foreign_tokenizer is not None:
+                # text_cfg.hf_tokenizer_name: the tower's vocabulary is another tokenizer's; CLIP's BPE ids would be wrong for it
+                raise ValueError(f"this text tower was configured for the tokenizer {self._foreign_tokenizer!r} "
+                                 "(text_cfg.hf_tokenizer_name): the package's CLIP BPE has the wrong vocabulary for it -- "
+                                 "tokenize with that tokenizer and pass the token ids")
             if self._bpe is None:
                 from .tokenizer import BpeTokenizer      # raises FileNotFoundError with instructions if no merge table
                 self._bpe = BpeTokenizer(self.tokenizer_vocab, self.cfg.text.context_length)

@@ -497,31 +497,40 @@ def im2col(images, patches, P: int, ld_out: Optional[int] = None, keep=None):
 def embed_ln_fwd(patch_out, cls, pos, gamma, beta, x, mean, rstd, B: int, L: int, d: int, eps: float = 1e-5, keep=None):
     """class token + positional embedding + ln_pre -> the residual stream ``x`` [B*L, d]: fp32, or bf16 (sc_embed_ln_fwd_x16)
     when the stream is kept in bf16.  ``keep`` (int32 [B, L - 1], FLIP patch dropout): ``patch_out`` holds the kept patches'
-    rows only and token t > 0 takes position keep[b, t - 1] + 1 of ``pos`` (sc_embed_ln_fwd_keep / _keep_x16)."""
+    rows only and token t > 0 takes position keep[b, t - 1] + 1 of ``pos`` (sc_embed_ln_fwd_keep / _keep_x16).
+    ``gamma`` None (a tower built with ``no_ln_pre``): no LayerNorm, ``x`` = class token / patch rows + positions; ``beta``,
+    ``mean`` and ``rstd`` are ignored (may be None) and never written."""
     x16 = x.dtype == torch.bfloat16
+    if gamma is None:
+        beta = None
     _req(x, torch.bfloat16 if x16 else torch.float32, "x")
     if keep is not None:
         _req_keep(keep, B, L - 1)
         what = "sc_embed_ln_fwd_keep_x16" if x16 else "sc_embed_ln_fwd_keep"
-        check(getattr(_lib.lib(), what)(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(), gamma.data_ptr(),
-                                        beta.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, L,
+        check(getattr(_lib.lib(), what)(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(), _ptr(gamma),
+                                        _ptr(beta), x.data_ptr(), _ptr(mean), _ptr(rstd), B, L,
                                         pos.shape[0] - 1, d, float(eps), _stream()), what)
         return x
     if x16:
         fn, what = _lib.lib().sc_embed_ln_fwd_x16, "sc_embed_ln_fwd_x16"
     else:
         fn, what = _lib.lib().sc_embed_ln_fwd, "sc_embed_ln_fwd"
-    check(fn(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr(), x.data_ptr(),
-             mean.data_ptr(), rstd.data_ptr(), B, L, d, float(eps), _stream()), what)
+    check(fn(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), _ptr(gamma), _ptr(beta), x.data_ptr(),
+             _ptr(mean), _ptr(rstd), B, L, d, float(eps), _stream()), what)
     return x
 
 
 def embed_ln_bwd(dres, patch_out, cls, pos, mean, rstd, gamma, dpatch_bf16, dgamma, dbeta, dpos, dcls, B, L, d, keep=None,
                  slot=None):
     """``keep`` / ``slot`` (int32 [B, L - 1] / [B, n], FLIP patch dropout): the backward of the dropping forward at L = K + 1
-    tokens; ``dpos`` has all n + 1 rows, exact zeros where no sample kept the patch (sc_embed_ln_bwd_keep)."""
+    tokens; ``dpos`` has all n + 1 rows, exact zeros where no sample kept the patch (sc_embed_ln_bwd_keep).
+    ``gamma`` None (``no_ln_pre``): d(token) is ``dres`` itself, left untouched; ``dpatch_bf16`` is the bf16 rounding of its
+    rows t > 0; ``mean`` / ``rstd`` / ``dgamma`` / ``dbeta`` are ignored (may be None), no workspace is used."""
     l = _lib.lib()
-    ws = workspace(l.sc_embed_ln_bwd_ws_floats(B, L, d), dres.device, "embed")
+    if gamma is None:
+        mean = rstd = dgamma = dbeta = ws = None
+    else:
+        ws = workspace(l.sc_embed_ln_bwd_ws_floats(B, L, d), dres.device, "embed")
     if keep is not None:
         n = pos.shape[0] - 1
         _req_keep(keep, B, L - 1)
@@ -531,14 +540,56 @@ def embed_ln_bwd(dres, patch_out, cls, pos, mean, rstd, gamma, dpatch_bf16, dgam
         if dpos.numel() != (n + 1) * d:
             raise ValueError(f"dpos: expected {(n + 1) * d} elements, got {dpos.numel()}")
         check(l.sc_embed_ln_bwd_keep(dres.data_ptr(), patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), keep.data_ptr(),
-                                     slot.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                     dpatch_bf16.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), dpos.data_ptr(),
-                                     dcls.data_ptr(), ws.data_ptr(), B, L, n, d, _stream()), "sc_embed_ln_bwd_keep")
+                                     slot.data_ptr(), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                     dpatch_bf16.data_ptr(), _ptr(dgamma), _ptr(dbeta), dpos.data_ptr(),
+                                     dcls.data_ptr(), _ptr(ws), B, L, n, d, _stream()), "sc_embed_ln_bwd_keep")
         return
-    check(l.sc_embed_ln_bwd(dres.data_ptr(), patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), mean.data_ptr(),
-                            rstd.data_ptr(), gamma.data_ptr(), dpatch_bf16.data_ptr(), dgamma.data_ptr(),
-                            dbeta.data_ptr(), dpos.data_ptr(), dcls.data_ptr(), ws.data_ptr(), B, L, d, _stream()),
+    check(l.sc_embed_ln_bwd(dres.data_ptr(), patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), _ptr(mean),
+                            _ptr(rstd), _ptr(gamma), dpatch_bf16.data_ptr(), _ptr(dgamma),
+                            _ptr(dbeta), dpos.data_ptr(), dcls.data_ptr(), _ptr(ws), B, L, d, _stream()),
           "sc_embed_ln_bwd")
+
+
+# ------------------------------------------------------------------------------------------ token mean pooling
+def _req_rows(t: torch.Tensor, name: str) -> bool:
+    """bf16 or fp32 contiguous device rows -> is it bf16?"""
+    if t.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"{name}: expected bfloat16 or float32, got {t.dtype}")
+    _req(t, t.dtype, name)
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t.dtype == torch.bfloat16
+
+
+def token_pool_fwd(x, B: int, L: int, t0: int, d: int, mean_f32=None, mean_bf16=None):
+    """mean[b] = mean over tokens t >= t0 of the contiguous rows ``x`` [B, L, d] (bf16 or fp32), fp32 accumulation in a fixed
+    order; written to ``mean_f32`` [B, d] and / or ``mean_bf16`` [B, d] (sc_token_pool_fwd)."""
+    xb = _req_rows(x, "x")
+    if x.numel() != B * L * d:
+        raise ValueError(f"x: expected {B * L * d} elements, got {x.numel()}")
+    for t, dt, name in ((mean_f32, torch.float32, "mean_f32"), (mean_bf16, torch.bfloat16, "mean_bf16")):
+        if t is not None:
+            _req(t, dt, name)
+            if t.numel() != B * d or not t.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous [{B}, {d}] tensor")
+    check(_lib.lib().sc_token_pool_fwd(x.data_ptr(), int(xb), B, L, t0, d, _ptr(mean_f32), _ptr(mean_bf16), _stream()),
+          "sc_token_pool_fwd")
+    return mean_f32 if mean_f32 is not None else mean_bf16
+
+
+def token_pool_bwd(d_mean, B: int, L: int, t0: int, d: int, dx_f32=None, dx_bf16=None):
+    """Backward of token_pool_fwd into contiguous [B, L, d] rows: exact zeros for t < t0, ``d_mean / (L - t0)`` elsewhere, as
+    fp32 (``dx_f32``) and / or its bf16 rounding (``dx_bf16``).  Every element is written (sc_token_pool_bwd)."""
+    db = _req_rows(d_mean, "d_mean")
+    if d_mean.numel() != B * d:
+        raise ValueError(f"d_mean: expected {B * d} elements, got {d_mean.numel()}")
+    for t, dt, name in ((dx_f32, torch.float32, "dx_f32"), (dx_bf16, torch.bfloat16, "dx_bf16")):
+        if t is not None:
+            _req(t, dt, name)
+            if t.numel() != B * L * d or not t.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous [{B}, {L}, {d}] tensor")
+    check(_lib.lib().sc_token_pool_bwd(d_mean.data_ptr(), int(db), B, L, t0, d, _ptr(dx_f32), _ptr(dx_bf16), _stream()),
+          "sc_token_pool_bwd")
 
 
 # ------------------------------------------------------------------------------------------ contrastive head

@@ -88,8 +88,9 @@ def build_specs(cfg: ModelCfg) -> List[ParamSpec]:
     specs.append(ParamSpec("visual.conv1.weight", (d, 3, v.patch_size, v.patch_size), f"uniform:{1.0 / math.sqrt(fan_in)}"))
     specs.append(ParamSpec("visual.class_embedding", (d,), f"normal:{d ** -0.5}"))
     specs.append(ParamSpec("visual.positional_embedding", (v.tokens, d), f"normal:{d ** -0.5}"))
-    specs.append(ParamSpec("visual.ln_pre.weight", (d,), "ones"))
-    specs.append(ParamSpec("visual.ln_pre.bias", (d,), "zeros"))
+    if not getattr(v, "no_ln_pre", False):      # vision_cfg.no_ln_pre: nn.Identity in the reference, no keys in its state_dict
+        specs.append(ParamSpec("visual.ln_pre.weight", (d,), "ones"))
+        specs.append(ParamSpec("visual.ln_pre.bias", (d,), "zeros"))
     for i in range(v.layers):
         specs += _block_specs(f"visual.transformer.resblocks.{i}.", d, int(d * v.mlp_ratio))
     specs.append(ParamSpec("visual.ln_post.weight", (d,), "ones"))

@@ -29,9 +29,17 @@ def _head_fwd(t, x: torch.Tensor, ldx: Optional[int] = None) -> torch.Tensor:
     ln_w, ln_b, proj = t.param_names_head()
     pooled = bf.get("pooled", (B, d), BF16)
     ops.layernorm_fwd(x, s.p(ln_w), s.p(ln_b), pooled, bf.get("m_post", (B,), F32), bf.get("r_post", (B,), F32), B, d, ldx=ldx)
+    return _proj_fwd(t, pooled)
+
+
+def _proj_fwd(t, pooled: torch.Tensor) -> torch.Tensor:
+    """Tail of ``_head_fwd``: the normalised pooled rows ``pooled`` (bf16 [B, d], the tower's "pooled" buffer) -> projection ->
+    L2 normalise."""
+    s, bf, B, d, D = t.s, t.bufs, t.B, t.d, t.D
+    proj = t.param_names_head()[2]
     f_raw = bf.get("f_raw", (B, D), F32)
     ops.gemm(ops.NT, ops.EPI_F32, pooled, s.copies[proj].wf, f_raw, M=B, N=D, K=d)
-    t.f = torch.empty((B, D), dtype=F32, device=x.device)
+    t.f = torch.empty((B, D), dtype=F32, device=pooled.device)
     ops.l2norm_fwd(f_raw, t.f, None, bf.get("inv", (B,), F32), B, D)
     return t.f
 
@@ -53,10 +61,21 @@ class PatchTransformerTower:
     attention blocks + ln_post on the class token (pool 'tok') + output projection + L2 normalise.  The image tower
     (VisionTransformer, src/open_clip/transformer.py:583-918) and the gene transformer (configs[4]; 1-D patches of the
     expression vector) are both instances: they differ in how the [B * patches, patch_dim] operand is formed
-    (``_patchify``) and in the parameter-name prefix."""
+    (``_patchify``) and in the parameter-name prefix.
+
+    The image tower also takes the reference's other head shapes (vision_cfg.pool_type / no_ln_pre / final_ln_after_pool,
+    transformer.py:594-603,652,773-823); the gene transformer keeps ln_pre and 'tok':
+      * ``no_ln_pre``: the stem adds class token and positions and applies no LayerNorm (no ln_pre parameters exist);
+      * ``pool_type == "avg"``: the last block runs at full width and the pooled row is the mean of the PATCH tokens
+        (ops.token_pool_fwd, t0 = 1; after patch dropout: of the kept ones) -- with ``final_ln_after_pool`` (CLIPA) ln_post is
+        applied to that mean, without it to every token before the mean;
+      * ``pool_type == "tok"`` with ``final_ln_after_pool`` is today's path: LayerNorm is per row."""
 
     prefix = "visual."
     quick_gelu = False          # set by the subclass before super().__init__: only the reference's towers take the config flag
+    pool_type = "tok"           # likewise: vision_cfg.pool_type / no_ln_pre / final_ln_after_pool
+    no_ln_pre = False
+    final_ln_after_pool = False
 
     def __init__(self, cfg: ModelCfg, store: ParamStore, width: int, heads: int, layers: int, mlp_ratio: float,
                  tokens: int, patch_dim: int):
@@ -66,7 +85,7 @@ class PatchTransformerTower:
         self.kp = patch_dim
         self.kp_pad = store.copies[self.prefix + "conv1.weight"].k_pad
         self.stack = TransformerStack(store, self.prefix + "transformer.resblocks.", width, heads, layers,
-                                      int(width * mlp_ratio), causal=False, cls_only_last=True, res16_ok=True,
+                                      int(width * mlp_ratio), causal=False, cls_only_last=self.pool_type == "tok", res16_ok=True,
                                       quick_gelu=self.quick_gelu)
         self.bufs = _Bufs(store.device)
         # state of the last forward, read by its backward: the token count of THAT pass (K + 1 when patches were dropped) and
@@ -86,8 +105,8 @@ class PatchTransformerTower:
         return [self._n("ln_post.weight"), self._n("ln_post.bias"), self._n("proj")]
 
     def param_names_stem(self) -> List[str]:
-        return [self._n("conv1.weight"), self._n("class_embedding"), self._n("positional_embedding"),
-                self._n("ln_pre.weight"), self._n("ln_pre.bias")]
+        names = [self._n("conv1.weight"), self._n("class_embedding"), self._n("positional_embedding")]
+        return names if self.no_ln_pre else names + [self._n("ln_pre.weight"), self._n("ln_pre.bias")]
 
     def _patchify(self, x: torch.Tensor) -> torch.Tensor:
         """-> bf16 [B * (L - 1), kp_pad] patch rows (sets self.B)."""
@@ -109,14 +128,37 @@ class PatchTransformerTower:
         # under bf16-mixed) instead of an fp32 copy that a cast pass then halves (310 MB of traffic per step at ViT-B/16)
         r16 = self.stack.res16_ok and _res_stream_bf16(self.stack.res_stream) and os.environ.get("SC_STEM_BF16", "1") != "0"
         x0 = bf.get("x0.16", (M, d), BF16) if r16 else bf.get("x0", (M, d), F32)
-        ops.embed_ln_fwd(patch_out, s.p(self._n("class_embedding")), s.p(self._n("positional_embedding")),
-                         s.p(self._n("ln_pre.weight")), s.p(self._n("ln_pre.bias")), x0,
-                         bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32), B, L, d, keep=keep)
+        if self.no_ln_pre:          # the row kernels' "no LN" body: no gamma, no statistics
+            ops.embed_ln_fwd(patch_out, s.p(self._n("class_embedding")), s.p(self._n("positional_embedding")), None, None, x0,
+                             None, None, B, L, d, keep=keep)
+        else:
+            ops.embed_ln_fwd(patch_out, s.p(self._n("class_embedding")), s.p(self._n("positional_embedding")),
+                             s.p(self._n("ln_pre.weight")), s.p(self._n("ln_pre.bias")), x0,
+                             bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32), B, L, d, keep=keep)
         xf = self.stack.forward(x0, B, L)
         self.xf = xf
         s.wait_names(self.param_names_head())
+        if self.pool_type == "avg":
+            return self._head_fwd_avg(xf, B, L)
         self.x_ld = d if self.stack.cls_only_last else L * d          # xf is compact [B, d] in CLS-only mode
         return _head_fwd(self, xf, ldx=self.x_ld)
+
+    def _head_fwd_avg(self, xf: torch.Tensor, B: int, L: int) -> torch.Tensor:
+        """Head of an average-pooled tower over the full-width output ``xf`` [B * L, d] of the last block."""
+        s, d, bf = self.s, self.d, self.bufs
+        if self.final_ln_after_pool:
+            # CLIPA order (transformer.py:816-818): mean of the patch tokens, then ln_post on the B mean rows
+            mean = bf.get("pool_mean", (B, d), F32)
+            ops.token_pool_fwd(xf, B, L, 1, d, mean_f32=mean)
+            return _head_fwd(self, mean, ldx=d)
+        # transformer.py:820-821: ln_post on every token, then the mean of the patch tokens' rows
+        ln_w, ln_b, _ = self.param_names_head()
+        M = B * L
+        y = bf.get("ln_post_all", (M, d), BF16)
+        ops.layernorm_fwd(xf, s.p(ln_w), s.p(ln_b), y, bf.get("m_post_all", (M,), F32), bf.get("r_post_all", (M,), F32), M, d)
+        pooled = bf.get("pooled", (B, d), BF16)
+        ops.token_pool_fwd(y, B, L, 1, d, mean_bf16=pooled)
+        return _proj_fwd(self, pooled)
 
     def raw_features(self) -> torch.Tensor:
         """Projected features of the last forward before F.normalize (encode_image(normalize=False))."""
@@ -131,6 +173,34 @@ class PatchTransformerTower:
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
         d_pooled = _head_bwd(self, d_f)
+        head_bwd = self._head_bwd_avg if self.pool_type == "avg" else self._head_bwd_tok
+        dres, dres_bf = head_bwd(d_pooled, B, L)
+        if on_bucket is not None:
+            on_bucket(self.param_names_head())
+        cb = (lambda i: on_bucket(self.stack.layer_param_names(i))) if on_bucket is not None else None
+        dres = self.stack.backward(dres, dres_bf, last_bias_colsum_done=True, on_layer_done=cb)
+        # stem: ln_pre / positional / class embedding / patch embedding (no gradient flows to the input)
+        dpatch = bf.get("dpatch", (Mp, d), BF16)
+        if self.no_ln_pre:
+            ops.embed_ln_bwd(dres, bf.get("patch_out", (Mp, d), F32), s.p(self._n("class_embedding")),
+                             s.p(self._n("positional_embedding")), None, None, None, dpatch, None, None,
+                             s.g(self._n("positional_embedding")), s.g(self._n("class_embedding")), B, L, d, keep=keep, slot=slot)
+        else:
+            ops.embed_ln_bwd(dres, bf.get("patch_out", (Mp, d), F32), s.p(self._n("class_embedding")),
+                             s.p(self._n("positional_embedding")), bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32),
+                             s.p(self._n("ln_pre.weight")), dpatch, s.g(self._n("ln_pre.weight")), s.g(self._n("ln_pre.bias")),
+                             s.g(self._n("positional_embedding")), s.g(self._n("class_embedding")), B, L, d, keep=keep, slot=slot)
+        gw = s.g(self._n("conv1.weight")).view(d, self.kp)
+        ops.gemm(ops.TN, ops.EPI_F32, dpatch, bf.get("patches", (Mp, self.kp_pad), BF16), gw, M=d, N=self.kp, K=Mp,
+                 splitk=_splitk_for(d, self.kp, Mp))
+        if on_bucket is not None:
+            on_bucket(self.param_names_stem())
+
+    def _head_bwd_tok(self, d_pooled: torch.Tensor, B: int, L: int):
+        """ln_post backward on the class-token rows (pool 'tok'): the residual gradient of the last block's output, the ln_post
+        gradients and the last block's c_proj.bias gradient.  Returns (dres, dres_bf)."""
+        s, d, bf = self.s, self.d, self.bufs
+        M = B * L
         last = self.n_layers - 1
         if self.stack.cls_only_last:
             # class-token-only last block: its fp32 residual gradient lives in the class-token rows of the FULL buffer
@@ -148,25 +218,37 @@ class PatchTransformerTower:
                           s.p(self._n("ln_post.weight")), dres, dres_bf, s.g(self._n("ln_post.weight")),
                           s.g(self._n("ln_post.bias")), s.g(self._n(f"transformer.resblocks.{last}.mlp.c_proj.bias")),
                           B, d, accumulate=False, ldx=self.x_ld, lddres=L * d, lddbf=ld)
-        if on_bucket is not None:
-            on_bucket(self.param_names_head())
-        cb = (lambda i: on_bucket(self.stack.layer_param_names(i))) if on_bucket is not None else None
-        dres = self.stack.backward(dres, dres_bf, last_bias_colsum_done=True, on_layer_done=cb)
-        # stem: ln_pre / positional / class embedding / patch embedding (no gradient flows to the input)
-        dpatch = bf.get("dpatch", (Mp, d), BF16)
-        ops.embed_ln_bwd(dres, bf.get("patch_out", (Mp, d), F32), s.p(self._n("class_embedding")),
-                         s.p(self._n("positional_embedding")), bf.get("m_pre", (M,), F32), bf.get("r_pre", (M,), F32),
-                         s.p(self._n("ln_pre.weight")), dpatch, s.g(self._n("ln_pre.weight")), s.g(self._n("ln_pre.bias")),
-                         s.g(self._n("positional_embedding")), s.g(self._n("class_embedding")), B, L, d, keep=keep, slot=slot)
-        gw = s.g(self._n("conv1.weight")).view(d, self.kp)
-        ops.gemm(ops.TN, ops.EPI_F32, dpatch, bf.get("patches", (Mp, self.kp_pad), BF16), gw, M=d, N=self.kp, K=Mp,
-                 splitk=_splitk_for(d, self.kp, Mp))
-        if on_bucket is not None:
-            on_bucket(self.param_names_stem())
+        return dres, dres_bf
+
+    def _head_bwd_avg(self, d_pooled: torch.Tensor, B: int, L: int):
+        """Mirror of ``_head_fwd_avg`` from d(pooled) [B, d] (bf16) down to the stack: writes EVERY element of the residual
+        gradient of the last block's output (fp32 ``dres`` and bf16 ``dres_bf``, no memset), the ln_post gradients and the last
+        block's c_proj.bias gradient.  Returns (dres, dres_bf)."""
+        s, d, bf = self.s, self.d, self.bufs
+        M = B * L
+        dres = bf.get("dres", (M, d), F32)
+        dres_bf = bf.get("dres_bf", (M, d), BF16)
+        ln_w, ln_b, _ = self.param_names_head()
+        bias_g = s.g(self._n(f"transformer.resblocks.{self.n_layers - 1}.mlp.c_proj.bias"))
+        if self.final_ln_after_pool:
+            # LayerNorm backward on the B mean rows; its column sum IS the c_proj.bias gradient: each of the n pooled rows of a
+            # sample receives d_mean / n
+            d_mean = bf.get("d_pool_mean", (B, d), F32)
+            ops.layernorm_bwd(d_pooled, bf.get("pool_mean", (B, d), F32), bf.get("m_post", (B,), F32),
+                              bf.get("r_post", (B,), F32), s.p(ln_w), d_mean, None, s.g(ln_w), s.g(ln_b), bias_g, B, d,
+                              accumulate=False)
+            ops.token_pool_bwd(d_mean, B, L, 1, d, dx_f32=dres, dx_bf16=dres_bf)
+        else:
+            dy = bf.get("d_ln_post_all", (M, d), BF16)
+            ops.token_pool_bwd(d_pooled, B, L, 1, d, dx_bf16=dy)
+            ops.layernorm_bwd(dy, self.xf, bf.get("m_post_all", (M,), F32), bf.get("r_post_all", (M,), F32), s.p(ln_w), dres,
+                              dres_bf, s.g(ln_w), s.g(ln_b), bias_g, M, d, accumulate=False)
+        return dres, dres_bf
 
 
 class VisionTower(PatchTransformerTower):
-    """VisionTransformer (pool 'tok', learnable pos-embed, ln_pre/ln_post, output projection) + L2 normalise."""
+    """VisionTransformer (pool 'tok' or 'avg', learnable pos-embed, ln_pre unless no_ln_pre, ln_post before or after the pool,
+    output projection) + L2 normalise."""
 
     prefix = "visual."
 
@@ -174,6 +256,11 @@ class VisionTower(PatchTransformerTower):
         v = cfg.vision
         self.v = v
         self.quick_gelu = bool(getattr(cfg, "quick_gelu", False))
+        self.pool_type = str(getattr(v, "pool_type", "tok"))
+        if self.pool_type not in ("tok", "avg"):
+            raise ValueError(f"vision pool_type {self.pool_type!r}: 'tok' or 'avg'")
+        self.no_ln_pre = bool(getattr(v, "no_ln_pre", False))
+        self.final_ln_after_pool = bool(getattr(v, "final_ln_after_pool", False))
         super().__init__(cfg, store, v.width, v.heads, v.layers, v.mlp_ratio, v.tokens, 3 * v.patch_size * v.patch_size)
         # FLIP patch dropout (vision_cfg.patch_dropout; PatchDropout, src/open_clip/transformer.py:48-89): a forward that will be
         # differentiated, on a net in training mode, keeps K of the n patch tokens.  SpatialClipNet.forward arms ``drop`` for that
@@ -328,8 +415,15 @@ class TextTower:
         self.cfg, self.t, self.s = cfg, t, store
         self.d, self.D, self.L, self.V = t.width, cfg.embed_dim, t.context_length, t.vocab_size
         self.stack = TransformerStack(store, "transformer.resblocks.", t.width, t.heads, t.layers,
-                                      int(t.width * t.mlp_ratio), causal=True, quick_gelu=bool(getattr(cfg, "quick_gelu", False)))
+                                      int(t.width * t.mlp_ratio), causal=not getattr(t, "no_causal_mask", False),
+                                      quick_gelu=bool(getattr(cfg, "quick_gelu", False)))
         self.bufs = _Bufs(store.device)
+        # text_cfg.pool_type (text_global_pool, src/open_clip/transformer.py:921-940): the pooled row is the one at text.argmax(-1)
+        # (EOT), the last or the first token; for the two fixed ones the index buffer is filled once per buffer, not per step
+        self.pool_type = str(getattr(t, "pool_type", "argmax"))
+        if self.pool_type not in ("argmax", "last", "first"):
+            raise ValueError(f"text pool_type {self.pool_type!r}: 'argmax', 'last' or 'first'")
+        self._eot_filled: Optional[torch.Tensor] = None
 
     def param_names_head(self) -> List[str]:
         return ["ln_final.weight", "ln_final.bias", "text_projection"]
@@ -352,7 +446,11 @@ class TextTower:
         xf = self.stack.forward(x0, B, L)
         s.wait_names(self.param_names_head())
         eot = bf.get("eot", (B,), torch.int32)
-        ops.argmax_rows(text, eot, B, L)
+        if self.pool_type == "argmax":
+            ops.argmax_rows(text, eot, B, L)
+        elif self._eot_filled is not eot:
+            eot.fill_(L - 1 if self.pool_type == "last" else 0)
+            self._eot_filled = eot
         xe = bf.get("x_eot", (B, d), F32)
         ops.gather_rows(xf, eot, L, xe, B, d)
         return _head_fwd(self, xe)
@@ -382,6 +480,6 @@ class TextTower:
         self.stack.backward(dres, dres_bf, last_bias_colsum_done=True, on_layer_done=cb)
         # scatter-add of the embedding gather: bit-reproducible by default (SC_EMBED_BWD_ATOMIC=1: the float-atomic kernel, A/B)
         ops.token_embed_bwd(self.text, dres, s.g("token_embedding.weight"), s.g("positional_embedding"), B, L, d, self.V,
-                            eot=bf.get("eot", (B,), torch.int32), deterministic=os.environ.get("SC_EMBED_BWD_ATOMIC", "0") != "1")
+                            eot=bf.get("eot", (B,), torch.int32) if self.stack.causal else None, deterministic=os.environ.get("SC_EMBED_BWD_ATOMIC", "0") != "1")
         if on_bucket is not None:
             on_bucket(self.param_names_stem())
