@@ -364,6 +364,25 @@ int sc_recall_hits(const float* z_image_rows, int G, int B, int col0, int* hits3
  * overwritten.  No float atomics: bit-identical across launches. */
 int sc_siglip_loss(float* z_inout, int B, int G, int col0, const float* logit_scale, const float* logit_bias,
                    float* rowpart, float* loss_out, float* d_scale, float* d_bias, int* recall_hits3, void* stream);
+/* DistillClipLoss (src/open_clip/loss.py:203-239) on the device.  z_s_inout[2][B][G] / z_t_inout[2][B][G]: cosine
+ * similarities of the student / the frozen teacher, image->text rows first, then text->image; the positives sit at
+ * column col0 + i (col0 = rank*B, or 0 for the [G,G] layout).  logit_scale / dist_logit_scale: the exponentiated scales
+ * (device scalars).  One rows launch: per row both log-sum-exps (max subtracted), CE = lse(x_s) - x_s[diag] and
+ * D = sum_j softmax(x_t)_j (lse(x_s) - x_s,j); dz_c = s (p_s - onehot) 0.5/B is written over z_s and
+ * dz_d = s (p_s - p_t) 0.5/B over z_t (the teacher is detached: its matrix is dead after the pass);
+ * rowpart[2B][4] = per-row {CE, D, sum dl_c z_s, sum dl_d z_s}.  A fixed-order finalize writes
+ * loss_out[4] = {contrastive, distill, CE_image, CE_text} and d_scale_c / d_scale_d (of the exponentiated student scale;
+ * each may be NULL).  Rows of G <= SC_DISTILL_RESIDENT_MAX_G columns are held in registers (each matrix read once),
+ * longer rows are re-read.  recall_hits3 (may be NULL) += R@1/5/10 of the image rows' diagonal block, counted before z_s
+ * is overwritten.  No float atomics: bit-identical across launches. */
+#define SC_DISTILL_RESIDENT_MAX_G 2048
+int sc_distill_resident_max_g(void);
+int sc_distill_loss(float* z_s_inout, float* z_t_inout, int B, int G, int col0, const float* logit_scale,
+                    const float* dist_logit_scale, float* rowpart, float* loss_out, float* d_scale_c, float* d_scale_d,
+                    int* recall_hits3, void* stream);
+/* out[n] = *ga * a[n] + *gb * b[n] (device scalars): the backward of the two-output distillation loss node in one launch. */
+int sc_axpby_scalars(const float* a, const float* ga, const float* b, const float* gb, float* out, long long n,
+                     void* stream);
 /* Validation-only zero-shot gene-expression metric (src/metrics/zero_shot.py:62-88): sample-wise
  * Pearson correlation of pred[rows, cols] (image_features @ gene_bank^T) against the rank-weighted targets, rows with
  * sqrt(sum pc^2) * sqrt(sum tc^2) <= 1e-6 score 0.  pcc[rows] (may be NULL); sum_count[0] += sum(pcc),

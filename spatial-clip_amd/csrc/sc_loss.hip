@@ -309,6 +309,134 @@ __global__ __launch_bounds__(256) void siglip_finalize_kernel(const float* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------- distillation loss
+// reference: src/open_clip/loss.py:203-239 (DistillClipLoss).  Row r = dir*B + i of the student's z_s[2][B][G] and the
+// frozen teacher's z_t[2][B][G] (cosine similarities): x_s = s*z_s, x_t = s_t*z_t, p = softmax over the row,
+//   CE_r = lse(x_s) - x_s[diag]                       d CE_r / d x_s = p_s - onehot(diag)      diag = col0 + i
+//   D_r  = sum_j p_t,j * (lse(x_s) - x_s,j)           d D_r  / d x_s = p_s - p_t               (teacher detached)
+// D_r is summed in the form above (every term >= 0) rather than as lse - sum p_t*x_s, which cancels at large scales.
+// One launch: both maxima, both exp-sums, then one pass that writes dz_c = s*(p_s - onehot)*0.5/B over z_s and
+// dz_d = s*(p_s - p_t)*0.5/B over z_t (the teacher matrix is dead afterwards) and the row's partials
+// {CE_r, D_r, sum_j dl_c*z_s, sum_j dl_d*z_s} (dl = dz / s).  A row of G <= SC_DISTILL_RESIDENT_MAX_G columns lives in
+// registers (DISTILL_NREG values of each matrix per thread, static indices: no scratch), so z_s and z_t are read once;
+// longer rows are re-read (from L2) for the second and third pass.  A p_t that underflows contributes an exact 0.
+constexpr int DISTILL_NREG = SC_DISTILL_RESIDENT_MAX_G / 256;
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(256) void distill_rows_kernel(float* __restrict__ zs, float* __restrict__ zt, int B, int G,
+                                                           int col0, const float* __restrict__ scale,
+                                                           const float* __restrict__ tscale,
+                                                           float* __restrict__ rowpart) {
+    __shared__ float sm[4];
+    const int r = blockIdx.x;  // dir*B + i
+    float* zsr = zs + (long long)r * G;
+    float* ztr = zt + (long long)r * G;
+    const float s = *scale, st = *tscale;
+    const int diag = col0 + (r % B);
+    const float c = 0.5f / (float)B;
+    float vs[DISTILL_NREG], vt[DISTILL_NREG];
+    float ms = -3.0e38f, mt = -3.0e38f;
+    if (RESIDENT) {
+#pragma unroll
+        for (int k = 0; k < DISTILL_NREG; ++k) {
+            const int j = threadIdx.x + k * 256;
+            vs[k] = j < G ? zsr[j] : 0.f;
+            vt[k] = j < G ? ztr[j] : 0.f;
+            if (j < G) { ms = fmaxf(ms, s * vs[k]); mt = fmaxf(mt, st * vt[k]); }
+        }
+    } else {
+        for (int j = threadIdx.x; j < G; j += 256) { ms = fmaxf(ms, s * zsr[j]); mt = fmaxf(mt, st * ztr[j]); }
+    }
+    ms = block_max(ms, sm);
+    mt = block_max(mt, sm);
+    float ses = 0.f, set_ = 0.f;
+    if (RESIDENT) {
+#pragma unroll
+        for (int k = 0; k < DISTILL_NREG; ++k) {
+            const int j = threadIdx.x + k * 256;
+            if (j < G) { ses += expf(fmaf(s, vs[k], -ms)); set_ += expf(fmaf(st, vt[k], -mt)); }
+        }
+    } else {
+        for (int j = threadIdx.x; j < G; j += 256) { ses += expf(fmaf(s, zsr[j], -ms)); set_ += expf(fmaf(st, ztr[j], -mt)); }
+    }
+    ses = block_sum(ses, sm);
+    set_ = block_sum(set_, sm);
+    const float lns = logf(ses);
+    const float inv_s = 1.0f / ses, inv_t = 1.0f / set_;
+    float ce = 0.f, dd = 0.f, sc_ = 0.f, sd_ = 0.f;
+    // exponents as fma(s, z, -max): the product is not rounded at the magnitude of the logit (ulp 7.6e-6 at 100), and the
+    // rounding of the maximum itself cancels in e / sum(e)
+    auto body = [&](int j, float a, float b) {
+        const float xs = fmaf(s, a, -ms);                       // x_s - max <= ~0
+        const float ps = expf(xs) * inv_s;
+        const float pt = expf(fmaf(st, b, -mt)) * inv_t;
+        const float nl = lns - xs;                              // -log p_s = lse - x_s
+        const bool on = j == diag;
+        if (on) ce = nl;
+        dd += pt * nl;
+        const float dlc = c * (ps - (on ? 1.0f : 0.0f));
+        const float dld = c * (ps - pt);
+        sc_ += dlc * a;
+        sd_ += dld * a;
+        zsr[j] = s * dlc;
+        ztr[j] = s * dld;
+    };
+    if (RESIDENT) {
+#pragma unroll
+        for (int k = 0; k < DISTILL_NREG; ++k) {
+            const int j = threadIdx.x + k * 256;
+            if (j < G) body(j, vs[k], vt[k]);
+        }
+    } else {
+        for (int j = threadIdx.x; j < G; j += 256) body(j, zsr[j], ztr[j]);
+    }
+    ce = block_sum(ce, sm);        // one thread holds the diagonal, the others 0
+    dd = block_sum(dd, sm);
+    sc_ = block_sum(sc_, sm);
+    sd_ = block_sum(sd_, sm);
+    if (threadIdx.x == 0) {
+        float* o = rowpart + (long long)r * 4;
+        o[0] = ce;
+        o[1] = dd;
+        o[2] = sc_;
+        o[3] = sd_;
+    }
+}
+
+// loss_out = {contrastive, distill, CE_image, CE_text}; d_scale_c / d_scale_d of the exponentiated student scale
+__global__ __launch_bounds__(256) void distill_finalize_kernel(const float* __restrict__ rowpart, int B,
+                                                               float* __restrict__ loss_out, float* __restrict__ dsc,
+                                                               float* __restrict__ dsd) {
+    __shared__ float sm[4];
+    float ce0 = 0.f, ce1 = 0.f, d0 = 0.f, d1 = 0.f, gc = 0.f, gd = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const float* a = rowpart + (long long)i * 4;
+        const float* b = rowpart + (long long)(B + i) * 4;
+        ce0 += a[0];
+        ce1 += b[0];
+        d0 += a[1];
+        d1 += b[1];
+        gc += a[2] + b[2];
+        gd += a[3] + b[3];
+    }
+    ce0 = block_sum(ce0, sm) / B;
+    ce1 = block_sum(ce1, sm) / B;
+    d0 = block_sum(d0, sm) / B;
+    d1 = block_sum(d1, sm) / B;
+    gc = block_sum(gc, sm);
+    gd = block_sum(gd, sm);
+    if (threadIdx.x == 0) {
+        if (loss_out) {
+            loss_out[0] = 0.5f * (ce0 + ce1);
+            loss_out[1] = 0.5f * (d0 + d1);
+            loss_out[2] = ce0;
+            loss_out[3] = ce1;
+        }
+        if (dsc) *dsc = gc;
+        if (dsd) *dsd = gd;
+    }
+}
+
 __global__ void exp_scalar_kernel(const float* __restrict__ x, float* __restrict__ y) { *y = __expf(*x); }
 __global__ void exp_scalar_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
                                       float mult) {
@@ -432,6 +560,54 @@ extern "C" int sc_siglip_loss(float* z_inout, int B, int G, int col0, const floa
     siglip_rows_kernel<<<B, 256, 0, st>>>(z_inout, B, G, col0, logit_scale, logit_bias, rowpart);
     SC_LAUNCH_CHECK();
     siglip_finalize_kernel<<<1, 256, 0, st>>>(rowpart, B, loss_out, dscale, dbias);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_distill_resident_max_g(void) { return SC_DISTILL_RESIDENT_MAX_G; }
+
+extern "C" int sc_distill_loss(float* z_s_inout, float* z_t_inout, int B, int G, int col0, const float* logit_scale,
+                               const float* dist_logit_scale, float* rowpart, float* loss_out, float* d_scale_c,
+                               float* d_scale_d, int* recall_hits3, void* stream) {
+    SC_CHECK(B > 0 && G >= B && col0 >= 0 && (long long)col0 + B <= G, "sc_distill_loss: bad shape B=%d G=%d col0=%d", B,
+             G, col0);
+    SC_CHECK(z_s_inout != nullptr && z_t_inout != nullptr && logit_scale != nullptr && dist_logit_scale != nullptr &&
+                 rowpart != nullptr, "sc_distill_loss: null argument");
+    SC_CHECK(z_s_inout != z_t_inout, "sc_distill_loss: the student and teacher matrices must be distinct buffers");
+    hipStream_t st = (hipStream_t)stream;
+    if (recall_hits3) {     // ranks of the image rows' diagonal block, read before z_s is overwritten with dz_c
+        recall_kernel<<<B, 256, 0, st>>>(z_s_inout, G, B, col0, recall_hits3);
+        SC_LAUNCH_CHECK();
+    }
+    if (G <= SC_DISTILL_RESIDENT_MAX_G)
+        distill_rows_kernel<true><<<2 * B, 256, 0, st>>>(z_s_inout, z_t_inout, B, G, col0, logit_scale, dist_logit_scale,
+                                                         rowpart);
+    else
+        distill_rows_kernel<false><<<2 * B, 256, 0, st>>>(z_s_inout, z_t_inout, B, G, col0, logit_scale,
+                                                          dist_logit_scale, rowpart);
+    SC_LAUNCH_CHECK();
+    distill_finalize_kernel<<<1, 256, 0, st>>>(rowpart, B, loss_out, d_scale_c, d_scale_d);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// out[i] = *ga * a[i] + *gb * b[i] : the backward of the two-output distillation loss node (upstream gradients ga, gb of the
+// contrastive and the distillation term, device scalars, applied to the two gradient buffers the head formed for 1 and 1)
+__global__ void axpby_scalars_kernel(const float* __restrict__ a, const float* __restrict__ ga,
+                                     const float* __restrict__ b, const float* __restrict__ gb, float* __restrict__ out,
+                                     long long n) {
+    const float fa = *ga, fb = *gb;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = fa * a[i] + fb * b[i];
+}
+
+extern "C" int sc_axpby_scalars(const float* a, const float* ga, const float* b, const float* gb, float* out,
+                                long long n, void* stream) {
+    SC_CHECK(n > 0 && a != nullptr && ga != nullptr && b != nullptr && gb != nullptr && out != nullptr,
+             "sc_axpby_scalars: bad arguments (n=%lld)", n);
+    long long blocks = (n + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    axpby_scalars_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(a, ga, b, gb, out, n);
     SC_LAUNCH_CHECK();
     return 0;
 }

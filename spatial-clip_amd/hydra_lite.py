@@ -28,6 +28,8 @@ TARGET_MAP = {
     "src.models.components.losses.ClipLoss": "spatial_clip_amd.losses.ClipLoss",
     "open_clip.loss.SigLipLoss": "spatial_clip_amd.losses.SigLipLoss",
     "open_clip.SigLipLoss": "spatial_clip_amd.losses.SigLipLoss",
+    "open_clip.loss.DistillClipLoss": "spatial_clip_amd.losses.DistillClipLoss",
+    "open_clip.DistillClipLoss": "spatial_clip_amd.losses.DistillClipLoss",
     "src.models.components.metrics.ContrastiveMetrics": "spatial_clip_amd.metrics.ContrastiveMetrics",
     "src.data.spatial_datamodule.SpatialClipDataModule": "spatial_clip_amd.data.SpatialClipDataModule",
     "open_clip.AugmentationCfg": "spatial_clip_amd.net.AugmentationCfg",

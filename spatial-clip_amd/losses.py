@@ -1,4 +1,4 @@
-"""ClipLoss / SpatialLoss with the reference's constructor kwargs, forward kwargs and return contract
+"""ClipLoss / SpatialLoss / SigLipLoss / DistillClipLoss with the reference's constructor kwargs, forward kwargs and return contract
 (``{"contrastive_loss": 0-d tensor}``), computed by the fused device-side contrastive head.
 
 Mirrors ``src/models/components/losses.py:11-141`` (SpatialLoss; ClipLoss wrapper over open_clip's ClipLoss,
@@ -12,7 +12,7 @@ from typing import Dict, Optional
 import torch
 
 from . import comm, ops
-from .contrastive import contrastive_forward_backward, siglip_forward_backward
+from .contrastive import contrastive_forward_backward, distill_forward_backward, siglip_forward_backward
 
 
 class _ContrastiveFn(torch.autograd.Function):
@@ -226,3 +226,90 @@ class SigLipLoss(_LossBase):
                 logit_bias: Optional[torch.Tensor] = None, output_dict: bool = False):
         loss = _SigLipFn.apply(image_features, text_features, logit_scale, logit_bias, self)
         return {"contrastive_loss": loss} if output_dict else loss
+
+
+class _DistillFn(torch.autograd.Function):
+    """One node, two outputs (contrastive_loss, distill_loss).  Forward forms both losses and, per term, the feature / scale
+    gradients for an upstream gradient of 1; backward is g_c * grads_c + g_d * grads_d -- exact for any pair of upstream
+    gradients, which one pre-summed gradient buffer would not be.  The teacher's features and scale get no gradient."""
+
+    @staticmethod
+    def forward(ctx, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
+                owner):
+        rank, W = comm.world()
+        dist_on = comm.is_dist()
+        img = image_features.detach().contiguous().float()
+        txt = text_features.detach().contiguous().float()
+        t_img = dist_image_features.detach().contiguous().float()
+        t_txt = dist_text_features.detach().contiguous().float()
+        B, D = img.shape
+        all_i = all_t = t_all_i = t_all_t = late = None
+        fg = owner.prefetched
+        if dist_on and fg is not None and fg.has("text", txt) and fg.has("image", img):
+            all_t = fg.take("text")[0]
+            late = lambda: fg.take("image")[0]
+        elif dist_on:
+            all_i, all_t = comm.gather_packed(img, txt, None, None)[:2]
+        if dist_on:             # the teacher's features travel like the student's (no prefetch: its forward is already over)
+            t_all_i, t_all_t = comm.gather_packed(t_img, t_txt, None, None)[:2]
+        s, s_t = logit_scale.detach(), dist_logit_scale.detach()
+        if dist_on and not owner.local_loss:
+            # loss.py:119-121: every rank forms the full [G,G] logits of the global batch (labels arange(G))
+            if late is not None:
+                all_i = late()
+            res = distill_forward_backward(all_i, all_t, s, t_all_i, t_all_t, s_t, rank=0, recall_hits=owner.recall_hits,
+                                           recall_rows=(rank * B, B))
+            terms = []
+            for tag in ("c", "d"):      # the reduce-scatter operand does not depend on the upstream gradients per term only
+                d_all = res["d_all_" + tag]
+                tot = torch.cat([res["d_image_" + tag] + d_all[:, :D], res["d_text_" + tag] + d_all[:, D:]], dim=1)
+                both = comm.reduce_scatter_sum(tot) if owner.gather_with_grad else tot[rank * B:(rank + 1) * B]
+                terms.append((both[:, :D].contiguous(), both[:, D:].contiguous(), res["d_scale_" + tag]))
+            ctx.flat = None
+        else:
+            res = distill_forward_backward(img, txt, s, t_img, t_txt, s_t, all_image=all_i, all_text=all_t,
+                                           dist_all_image=t_all_i, dist_all_text=t_all_t, rank=rank if dist_on else 0,
+                                           recall_hits=owner.recall_hits, late_all_image=late, join_local=not dist_on)
+            terms = []
+            for tag in ("c", "d"):
+                d_i, d_t = res["d_image_" + tag], res["d_text_" + tag]
+                if dist_on and owner.gather_with_grad:
+                    # autograd of torch.distributed.nn.all_gather (loss.py:50-52), one reduce-scatter per term
+                    both = comm.reduce_scatter_sum(res["d_all_" + tag])
+                    d_i, d_t = d_i + both[:, :D], d_t + both[:, D:]
+                terms.append((d_i, d_t, res["d_scale_" + tag]))
+            flat = not (dist_on and owner.gather_with_grad)
+            ctx.flat = (res["grads_c"], res["grads_d"]) if flat else None
+        ctx.B, ctx.D = B, D
+        ctx.save_for_backward(*terms[0], *terms[1])
+        owner.last = res
+        return res["contrastive_loss"], res["distill_loss"]
+
+    @staticmethod
+    def backward(ctx, g_c, g_d):
+        g_c = g_c.detach().reshape(1).float()
+        g_d = g_d.detach().reshape(1).float()
+        if ctx.flat is not None and g_c.is_cuda:     # both terms are flat buffers: one launch forms g_c * grads_c + g_d * grads_d
+            a, b = ctx.flat
+            out = ops.axpby_scalars(a, g_c, b, g_d, torch.empty_like(a))
+            n = ctx.B * ctx.D
+            return out[:n].view(ctx.B, ctx.D), out[n:2 * n].view(ctx.B, ctx.D), out[2 * n], None, None, None, None
+        i_c, t_c, s_c, i_d, t_d, s_d = ctx.saved_tensors
+        return i_c * g_c + i_d * g_d, t_c * g_c + t_d * g_d, (s_c * g_c + s_d * g_d).reshape(()), None, None, None, None
+
+
+class DistillClipLoss(ClipLoss):
+    """``DistillClipLoss(local_loss, gather_with_grad, cache_labels, rank, world_size, use_horovod)`` (open_clip,
+    src/open_clip/loss.py:203-239): ClipLoss on the student plus the cross-entropy of the student's softmax rows against a
+    frozen teacher's, per direction.  ``forward(image_features, text_features, logit_scale, dist_image_features,
+    dist_text_features, dist_logit_scale, output_dict=False)`` returns ``(contrastive_loss, distill_loss)`` or the dict of
+    the two; the training loss is their sum.  The teacher's tensors are detached.  Layouts and gathers as in ClipLoss; the
+    teacher's features are gathered with a second packed all-gather, and with ``gather_with_grad`` each term has its own
+    reduce-scatter in forward (the operand is independent of the upstream gradient only per term)."""
+
+    def forward(self, image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
+                dist_image_features: torch.Tensor, dist_text_features: torch.Tensor, dist_logit_scale: torch.Tensor,
+                output_dict: bool = False):
+        c, d = _DistillFn.apply(image_features, text_features, logit_scale, dist_image_features, dist_text_features,
+                                dist_logit_scale, self)
+        return {"contrastive_loss": c, "distill_loss": d} if output_dict else (c, d)

@@ -6,7 +6,9 @@ loss kwargs, ``:44,55-61``), ``training_step(batch, batch_idx) -> loss``, ``vali
 ``self.logged`` (device scalars, no host sync) for the trainer's logger."""
 from __future__ import annotations
 
+import functools
 import inspect
+import operator
 import os
 from typing import Any, Callable, Dict, Optional
 
@@ -53,11 +55,59 @@ class StepOutput(dict):
         return [self[k] for k in self.keys()]
 
 
+TEACHER_KWARGS = ("dist_image_features", "dist_text_features", "dist_logit_scale")
+
+
+def loss_wants_teacher(loss_fn) -> bool:
+    """Does the loss's ``forward`` name ``dist_image_features`` (open_clip's DistillClipLoss does)?"""
+    return TEACHER_KWARGS[0] in inspect.signature(loss_fn.forward).parameters
+
+
+def check_teacher_binding(loss_fn, has_teacher: bool) -> None:
+    """A loss that takes teacher features needs ``dist_net``; a ``dist_net`` needs a loss that takes them.  ValueError."""
+    wants = loss_wants_teacher(loss_fn)
+    if wants and not has_teacher:
+        raise ValueError(f"{type(loss_fn).__name__}.forward takes dist_image_features: the module needs a teacher "
+                         "(dist_net=..., config key model.dist_net)")
+    if has_teacher and not wants:
+        raise ValueError(f"dist_net was given, but {type(loss_fn).__name__}.forward takes no dist_image_features: "
+                         "use loss=distill (DistillClipLoss) or drop model.dist_net")
+
+
+def check_teacher_config(student, teacher) -> None:
+    """The teacher sees the student's batch as it is (open_clip's training loop assumes identical transforms and tokenizer,
+    open_clip_train/main.py; here it is checked): same image size, same gene count / same text context length and
+    vocabulary.  ``student`` / ``teacher``: model_configs.ModelCfg.  ValueError naming the field that differs."""
+    def diff(what, a, b):
+        if a != b:
+            raise ValueError(f"distillation teacher: {what} differs from the student's ({b} vs {a}); the teacher is fed the "
+                             "student's batch, so both must read the same inputs")
+    diff("vision tower presence", student.vision is None, teacher.vision is None)
+    if student.vision is not None:
+        diff("image_size", student.vision.image_size, teacher.vision.image_size)
+    diff("second tower kind (gene / text)", student.gene is None, teacher.gene is None)
+    if student.gene is not None:
+        diff("n_genes", student.gene.n_genes, teacher.gene.n_genes)
+    else:
+        diff("text context_length", student.text.context_length, teacher.text.context_length)
+        diff("text vocab_size", student.text.vocab_size, teacher.text.vocab_size)
+
+
 class SpatialClipLitModule(torch.nn.Module):
     def __init__(self, net: SpatialClipNet, loss_fn: torch.nn.Module, optimizer_cfg: Callable, scheduler_cfg: Callable,
                  train_metrics: Optional[ContrastiveMetrics] = None, val_metrics: Optional[ContrastiveMetrics] = None,
-                 test_metrics: Optional[ContrastiveMetrics] = None, global_hvg_path: Optional[str] = None):
+                 test_metrics: Optional[ContrastiveMetrics] = None, global_hvg_path: Optional[str] = None,
+                 dist_net: Optional[SpatialClipNet] = None):
         super().__init__()
+        # distillation teacher (open_clip --distill-model / --distill-pretrained): frozen, evaluated under no_grad on the
+        # student's batch.  Kept OUT of the module tree (a tuple is not a submodule): parameters(), state_dict(), checkpoints,
+        # the optimiser and the DDP gradient exchange see the student alone, and module.train() cannot take it out of eval().
+        check_teacher_binding(loss_fn, dist_net is not None)
+        if dist_net is not None:
+            check_teacher_config(net.cfg, dist_net.cfg)
+            dist_net.eval()
+        self._teacher = (dist_net,)
+        self._loss_terms: Dict[str, torch.Tensor] = {}
         self.hparams = _HParams(optimizer_cfg=optimizer_cfg, scheduler_cfg=scheduler_cfg,
                                 global_hvg_path=global_hvg_path)      # save_hyperparameters(ignore=[net, loss_fn])
         self.net = net
@@ -79,6 +129,19 @@ class SpatialClipLitModule(torch.nn.Module):
     @property
     def device(self) -> torch.device:
         return self.net.device_
+
+    @property
+    def dist_net(self) -> Optional[SpatialClipNet]:
+        """The frozen distillation teacher, or None."""
+        return self._teacher[0]
+
+    def teacher_features(self, batch: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+        """``dist_image_features`` / ``dist_text_features`` / ``dist_logit_scale`` of the batch (open_clip_train/train.py:
+        134-137): the teacher's evaluation forward -- all tokens, no patch dropout, nothing kept for a backward."""
+        teacher = self.dist_net
+        with torch.no_grad():
+            out = teacher(batch["images"], batch["texts"])
+        return {k: out[k[len("dist_"):]].detach() for k in TEACHER_KWARGS}
 
     def log(self, name: str, value, sync_dist: bool = False, **kw) -> None:
         """Collects into ``self.logged`` (device scalars, no host sync).  ``sync_dist=True`` (the reference sets it on
@@ -109,9 +172,11 @@ class SpatialClipLitModule(torch.nn.Module):
         self.net.feature_gather = fg
         if hasattr(self.loss_fn, "prefetched"):
             self.loss_fn.prefetched = fg
+        # the teacher goes first: its forward is over before the student's writes the activations the backward will read
+        teacher_out = self.teacher_features(batch) if self.dist_net is not None else {}
         features = self.forward(batch["images"], batch["texts"])
         self.net.feature_gather = None
-        available_data = {**features, **batch}
+        available_data = {**features, **batch, **teacher_out}
         loss_input = {k: v for k, v in available_data.items() if k in self._loss_fn_arg_names}
         fused_hits = metrics is not None and hasattr(self.loss_fn, "recall_hits")
         if fused_hits:
@@ -121,9 +186,25 @@ class SpatialClipLitModule(torch.nn.Module):
         if fused_hits:
             metrics.add_hits(features["image_features"].shape[0])
             self.loss_fn.recall_hits = None
-        loss = loss_dict if isinstance(loss_dict, torch.Tensor) else loss_dict["contrastive_loss"]   # SigLipLoss: bare 0-d
+        terms = {}
+        if isinstance(loss_dict, torch.Tensor):         # SigLipLoss: bare 0-d
+            loss = loss_dict
+        elif isinstance(loss_dict, tuple):              # DistillClipLoss: (contrastive_loss, distill_loss)
+            terms = dict(zip(("contrastive_loss", "distill_loss"), loss_dict))
+        elif len(loss_dict) > 1:
+            terms = dict(loss_dict)
+        else:
+            loss = loss_dict["contrastive_loss"]
+        if terms:       # open_clip_train/train.py: total_loss = sum(losses.values()) -- a device add, no host sync
+            loss = functools.reduce(operator.add, terms.values())
+        self._loss_terms = terms
         return StepOutput({"loss": loss, "image_features": features["image_features"],
                            "text_features": features["text_features"], "logit_scale": features["logit_scale"]})
+
+    def _log_terms(self, prefix: str, **kw) -> None:
+        """``<prefix>contrastive_loss`` / ``<prefix>distill_loss`` beside ``<prefix>loss`` (their sum) for a multi-term loss."""
+        for name, value in self._loss_terms.items():
+            self.log(prefix + name, value, **kw)
 
     @staticmethod
     def local_logits(output: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -146,6 +227,7 @@ class SpatialClipLitModule(torch.nn.Module):
     def training_step(self, batch: Dict[str, Any], batch_idx: int) -> torch.Tensor:
         output = self.model_step(batch, self.train_metrics)
         self.log("train/loss", output["loss"], on_step=True, on_epoch=True, prog_bar=True, sync_dist=True)
+        self._log_terms("train/", on_step=True, on_epoch=True, sync_dist=True)
         self.log_dict(self.train_metrics, on_step=False, on_epoch=True, sync_dist=True)
         return output["loss"]
 
@@ -187,6 +269,7 @@ class SpatialClipLitModule(torch.nn.Module):
         with torch.no_grad():
             output = self.model_step(batch, self.val_metrics)
         self.log("val/loss", output["loss"], on_step=False, on_epoch=True, prog_bar=True, sync_dist=True)
+        self._log_terms("val/", on_step=False, on_epoch=True, sync_dist=True)
         self.log_dict(self.val_metrics, on_step=False, on_epoch=True, sync_dist=True)
         self._zero_shot_update(batch, output, "val/zero_shot_pcc")
 
@@ -194,6 +277,7 @@ class SpatialClipLitModule(torch.nn.Module):
         with torch.no_grad():
             output = self.model_step(batch, self.test_metrics)
         self.log("test/loss", output["loss"], on_step=False, on_epoch=True, sync_dist=True)
+        self._log_terms("test/", on_step=False, on_epoch=True, sync_dist=True)
         self.log_dict(self.test_metrics, on_step=False, on_epoch=True, sync_dist=True)
         self._zero_shot_update(batch, output, "test/zero_shot_pcc")
 

@@ -683,6 +683,41 @@ def siglip_loss(z, B, G, col0, scale, bias, rowpart, loss_out, dscale, dbias, hi
           "sc_siglip_loss")
 
 
+def distill_resident_max_g() -> int:
+    """Longest row (G) the distillation rows kernel keeps in registers (SC_DISTILL_RESIDENT_MAX_G); longer rows are re-read."""
+    return int(_lib.lib().sc_distill_resident_max_g())
+
+
+def distill_loss(z_s, z_t, B, G, col0, scale, dist_scale, rowpart, loss_out, dscale_c, dscale_d, hits3=None):
+    """DistillClipLoss rows pass + finalize: z_s <- dz_c, z_t <- dz_d (both [2, B, G] fp32, contiguous)."""
+    _req(z_s, torch.float32, "z_s"); _req(z_t, torch.float32, "z_t"); _req(rowpart, torch.float32, "rowpart")
+    _req(scale, torch.float32, "logit_scale"); _req(dist_scale, torch.float32, "dist_logit_scale")
+    _req(loss_out, torch.float32, "loss_out")
+    if tuple(z_s.shape) != (2, B, G) or tuple(z_t.shape) != (2, B, G) or not (z_s.is_contiguous() and z_t.is_contiguous()):
+        raise ValueError(f"distill_loss: z_s and z_t must be contiguous [2, {B}, {G}] tensors")
+    if rowpart.numel() < 8 * B or not rowpart.is_contiguous() or loss_out.numel() < 4 or not loss_out.is_contiguous():
+        raise ValueError("distill_loss: rowpart must hold [2B, 4] and loss_out 4 contiguous floats")
+    if scale.numel() != 1 or dist_scale.numel() != 1:
+        raise ValueError("distill_loss: the scales are one-element tensors")
+    if hits3 is not None:
+        _req(hits3, torch.int32, "recall_hits")
+    check(_lib.lib().sc_distill_loss(z_s.data_ptr(), z_t.data_ptr(), B, G, col0, scale.data_ptr(), dist_scale.data_ptr(),
+                                     rowpart.data_ptr(), loss_out.data_ptr(), _ptr(dscale_c), _ptr(dscale_d),
+                                     _ptr(hits3), _stream()), "sc_distill_loss")
+
+
+def axpby_scalars(a: torch.Tensor, ga: torch.Tensor, b: torch.Tensor, gb: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = ga * a + gb * b (ga, gb: one-element device tensors); contiguous fp32 of equal size."""
+    for t_, n in ((a, "a"), (ga, "ga"), (b, "b"), (gb, "gb"), (out, "out")):
+        _req(t_, torch.float32, n)
+    if not (a.is_contiguous() and b.is_contiguous() and out.is_contiguous()) or a.numel() != out.numel() \
+            or b.numel() != out.numel() or ga.numel() != 1 or gb.numel() != 1:
+        raise ValueError("axpby_scalars: contiguous tensors of equal size and one-element factors required")
+    check(_lib.lib().sc_axpby_scalars(a.data_ptr(), ga.data_ptr(), b.data_ptr(), gb.data_ptr(), out.data_ptr(),
+                                      a.numel(), _stream()), "sc_axpby_scalars")
+    return out
+
+
 def exp_scalar(x, y):
     check(_lib.lib().sc_exp_scalar(x.data_ptr(), y.data_ptr(), _stream()), "sc_exp_scalar")
     return y
