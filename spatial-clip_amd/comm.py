@@ -535,11 +535,17 @@ def reduce_scatter_sum(full: torch.Tensor) -> torch.Tensor:
 class GradBucketReducer:
     """Overlapped gradient reduction.  ``bucket_ready(lo, hi)`` is called by backward as soon as the flat-gradient
     range [lo, hi) is final; ranges are coalesced until ``bucket_floats`` is reached and then all-reduced
-    asynchronously.  ``finish()`` flushes and waits (on the compute stream, no host sync for nccl)."""
+    asynchronously.  ``finish()`` flushes and waits (on the compute stream, no host sync for nccl).
 
-    def __init__(self, flat_grad: torch.Tensor, bucket_floats: int = 16 * 1024 * 1024):
+    ``ranges``: the trainable (lo, hi) ranges of the flat buffer of a net with locked towers (``ParamStore.trainable_ranges``;
+    sorted, disjoint).  No float outside them is ever reduced -- as DDP reduces the gradients of trainable parameters only --
+    neither by an announced range nor by the complement ``finish()`` reduces.  Every rank locks the same towers, so every rank
+    skips the same ranges.  None: the whole buffer."""
+
+    def __init__(self, flat_grad: torch.Tensor, bucket_floats: int = 16 * 1024 * 1024, ranges=None):
         self.flat = flat_grad
         self.bucket_floats = bucket_floats
+        self.ranges = None if ranges is None or list(ranges) == [(0, flat_grad.numel())] else [(int(a), int(b)) for a, b in ranges]
         self.pending: Optional[Tuple[int, int]] = None
         self.works: List = []
         self.launched: List[Tuple[int, int]] = []
@@ -547,6 +553,14 @@ class GradBucketReducer:
     def bucket_ready(self, lo: int, hi: int) -> None:
         if not is_dist():
             return
+        if self.ranges is None:
+            self._ready(lo, hi)
+            return
+        for a, b in self.ranges:        # the trainable pieces of the announced range
+            if a < hi and lo < b:
+                self._ready(max(a, lo), min(b, hi))
+
+    def _ready(self, lo: int, hi: int) -> None:
         if self.pending is None:
             self.pending = (lo, hi)
         else:
@@ -599,13 +613,21 @@ class GradBucketReducer:
             self.pending = None
         covered = sum(hi - lo for lo, hi in self.launched)
         if covered < self.flat.numel():
-            # anything backward did not announce (e.g. logit_scale): reduce the complement in one go
+            # anything backward did not announce (e.g. logit_scale): reduce the complement in one go -- the complement WITHIN
+            # the trainable ranges of a net with locked towers
             done = sorted(self.launched)
-            pos = 0
-            for lo, hi in done + [(self.flat.numel(), self.flat.numel())]:
-                if lo > pos:
-                    self.works.append(self._reduce(pos, lo))
-                pos = max(pos, hi)
+            for rlo, rhi in (self.ranges if self.ranges is not None else [(0, self.flat.numel())]):
+                pos = rlo
+                for lo, hi in done:
+                    if hi <= pos:
+                        continue
+                    if lo >= rhi:
+                        break
+                    if lo > pos:
+                        self.works.append(self._reduce(pos, lo))
+                    pos = max(pos, hi)
+                if pos < rhi:
+                    self.works.append(self._reduce(pos, rhi))
         for w in self.works:
             if isinstance(w, torch.cuda.Event):
                 torch.cuda.current_stream(self.flat.device).wait_event(w)
@@ -881,8 +903,11 @@ def make_grad_exchange(store, bucket_floats: int = 16 * 1024 * 1024):
     on stderr and takes the all-reduce route -- same weights."""
     if not is_dist():
         return None
+    ranges = store.trainable_ranges() if hasattr(store, "trainable_ranges") else None
     if grad_exchange_mode() != "sharded":
-        return GradBucketReducer(store.grad, bucket_floats)
+        return GradBucketReducer(store.grad, bucket_floats, ranges)
+    if getattr(store, "locked", None):
+        raise ValueError("a locked tower with SC_GRAD_EXCHANGE=sharded is not supported: use SC_GRAD_EXCHANGE=allreduce")
     _, W = world()
     if store.total % (64 * W):
         sys.stderr.write(f"[spatial_clip_amd.comm] the parameter store ({store.total} floats) was built before the process group and is "

@@ -18,7 +18,7 @@ from typing import Any, Callable, Dict, List, Optional
 
 import torch
 
-from . import comm, ops, streams
+from . import comm, lock, ops, streams
 from .model_configs import (ModelCfg, check_attention_support, get_model_config, with_image_size, with_text_overrides,
                             with_vision_overrides)
 from .params import ParamStore
@@ -222,10 +222,20 @@ class SpatialClipNet(torch.nn.Module):
                  residual_stream: str = "bf16", init_logit_scale: Optional[float] = None,
                  init_logit_bias: Optional[float] = None, force_image_size: Optional[int] = None,
                  force_patch_dropout: Optional[float] = None, vision_cfg: Optional[Any] = None,
-                 text_cfg: Optional[Any] = None):
+                 text_cfg: Optional[Any] = None, lock_image: bool = False, lock_image_unlocked_groups: int = 0,
+                 lock_text: bool = False, lock_text_unlocked_layers: int = 0):
         super().__init__()
         if force_patch_dropout is not None:
             check_fraction(force_patch_dropout)     # ValueError outside [0, 1), before anything is built
+        if lock_image or lock_text:
+            # open_clip_train's --lock-image / --lock-image-unlocked-groups / --lock-text / --lock-text-unlocked-layers: the
+            # refusals come before anything is built (ValueError)
+            lock.check_lock_request(precision, comm.grad_exchange_mode())
+            lock.check_count(lock_image_unlocked_groups, "lock_image_unlocked_groups")
+            lock.check_count(lock_text_unlocked_layers, "lock_text_unlocked_layers")
+            early = model_cfg if model_cfg is not None else get_model_config(model_name, n_genes, gene_hidden)
+            if lock_text and early.text is None:
+                raise ValueError(self._NO_TEXT_TOWER.format(model_name))
         if aug_cfg is not None and not isinstance(aug_cfg, (dict, AugmentationCfg)) and not is_dataclass(aug_cfg) \
                 and not hasattr(aug_cfg, "items"):
             raise TypeError(f"Unsupported type for aug_cfg: {type(aug_cfg)}")     # spatial_clip_net.py:33-34
@@ -308,6 +318,45 @@ class SpatialClipNet(torch.nn.Module):
             stack = getattr(tower, "stack", None)
             if stack is not None:
                 stack.res_stream = residual_stream
+        if lock_image:
+            self.lock_image_tower(unlocked_groups=lock_image_unlocked_groups)
+        if lock_text:
+            self.lock_text_tower(unlocked_layers=lock_text_unlocked_layers)
+
+    # ------------------------------------------------------------------ locked towers (LiT)
+    _NO_TEXT_TOWER = ("lock_text_tower: {} has a gene tower in the text slot; the reference's text groups (embeddings, "
+                      "blocks, ln_final, text_projection) do not exist for it")
+
+    def _lock(self, tower, groups, unlocked: int) -> None:
+        lock.check_lock_request(self.precision, comm.grad_exchange_mode())
+        locked, free = lock.split_groups(groups, unlocked)
+        self.store.unlock(free)         # RuntimeError once an optimiser was built for this net
+        self.store.lock(locked)
+        tower.set_lock(unlocked)
+
+    def lock_image_tower(self, unlocked_groups: int = 0, freeze_bn_stats: bool = False) -> None:
+        """``CLIP.lock_image_tower`` (src/open_clip/model.py:304-306; VisionTransformer.lock, transformer.py:710-741): freeze
+        the image tower except its last ``unlocked_groups`` groups -- stem, each block but the last, [last block, ln_post],
+        proj.  ``freeze_bn_stats`` is accepted and ignored (no BatchNorm here).  Train / eval mode is untouched: patch dropout
+        of a locked tower still drops in training forwards.  Call before the optimiser is built."""
+        g = lock.check_count(unlocked_groups, "unlocked_groups")
+        v = self.cfg.vision
+        self._lock(self.vision, lock.vision_groups(v.layers, bool(getattr(v, "no_ln_pre", False))), g)
+
+    def lock_text_tower(self, unlocked_layers: int = 0, freeze_layer_norm: bool = True) -> None:
+        """``CLIP.lock_text_tower`` (src/open_clip/model.py:308-310; lock_text_tower, transformer.py:1360-1455): freeze the
+        text tower except its last ``unlocked_layers`` groups -- embeddings, each block but the last, [last block, ln_final],
+        text_projection.  ``freeze_layer_norm=False`` raises, as the reference asserts."""
+        if not freeze_layer_norm:
+            raise AssertionError("Unfreezing LayerNorm is not supported. LayerNorm treated like other weights.")
+        if self.cfg.text is None:
+            raise ValueError(self._NO_TEXT_TOWER.format(self.model_name))
+        k = lock.check_count(unlocked_layers, "unlocked_layers")
+        self._lock(self.second, lock.text_groups(self.cfg.text.layers), k)
+
+    def trainable_names(self) -> List[str]:
+        """Names (reference ``state_dict`` keys) of the parameters with ``requires_grad=True``, in forward order."""
+        return self.store.trainable_names()
 
     # ------------------------------------------------------------------ reference-facing helpers
     def set_grad_checkpointing(self, enable: bool = True) -> None:
@@ -534,9 +583,15 @@ class SpatialClipNet(torch.nn.Module):
             ts = streams.tower_stream(dev)
             ts.wait_stream(cur)                     # d_txt and the forward's activations are final on the chain
             with torch.cuda.stream(ts):
-                self.second.backward(d_txt, on_bucket=self._bucket)
-            self.vision.backward(d_img, on_bucket=self._bucket)
+                self._tower_backward(self.second, d_txt)
+            self._tower_backward(self.vision, d_img)
             cur.wait_stream(ts)
             return
-        self.second.backward(d_txt, on_bucket=self._bucket)
-        self.vision.backward(d_img, on_bucket=self._bucket)
+        self._tower_backward(self.second, d_txt)
+        self._tower_backward(self.vision, d_img)
+
+    def _tower_backward(self, tower, d_f) -> None:
+        """A tower with nothing trainable (locked with no unlocked group) has no backward."""
+        lk = getattr(tower, "lock", None)
+        if lk is None or lk.any_trainable:
+            tower.backward(d_f, on_bucket=self._bucket)

@@ -30,11 +30,22 @@ class FusedAdamW:
                              "self.parameters() un-grouped)")
         self.param_groups = [{"params": params, "lr": lr, "initial_lr": lr, "betas": tuple(betas), "eps": eps,
                               "weight_decay": weight_decay}]
-        n = self.store.total
+        # Locked towers (SpatialClipNet.lock_image_tower / lock_text_tower): Lightning still passes every parameter; the ones
+        # with requires_grad=False get what torch.optim.AdamW gives a parameter without .grad -- no update, no weight decay, no
+        # moments.  Every step form runs over the trainable ranges of the flat buffers (one range, the whole buffer, without a
+        # lock) and the moments are laid out compactly: range k starts at ``self._moff[k]``.
+        self.ranges: List[Tuple[int, int]] = list(self.store.trainable_ranges())
+        self._moff: List[int] = []
+        n = 0
+        for lo, hi in self.ranges:
+            self._moff.append(n)
+            n += hi - lo
+        self.store.optimizer_built = True       # the lock methods refuse from here on
         dev = self.store.device
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.norm_clip = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._range_partials: Optional[torch.Tensor] = None     # locked: 1024 fp64 sums of squares per trainable range
         self.step_count = 0
         self.exchange = None        # comm.ShardedGradExchange when this rank owns 1/W of every gradient bucket
         self._behind = None         # bucket plan of the replicated optimiser's overlapped form (_step_behind_forward)
@@ -52,6 +63,9 @@ class FusedAdamW:
         if not isinstance(exchange, comm.ShardedGradExchange):
             self.exchange = None
             return
+        if self.store.locked:
+            raise ValueError("FusedAdamW: a locked tower with the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not "
+                             "supported; use the all-reduce exchange")
         self.exchange = exchange
         n = exchange.shard_floats()
         dev = self.store.device
@@ -65,11 +79,23 @@ class FusedAdamW:
         finished from them and the gradient is not read a second time."""
         if max_norm is None or max_norm <= 0:
             return None
+        st = self.store
         if sumsq_partial is not None:
-            ops.grad_norm_final(sumsq_partial, 1024, grad_scale, max_norm, self.norm_clip)
-        else:
-            ops.grad_norm(self.store.grad, self.store.total, grad_scale, max_norm, self.norm_clip)
+            ops.grad_norm_final(sumsq_partial, sumsq_partial.numel(), grad_scale, max_norm, self.norm_clip)
+        elif self.ranges == [(0, st.total)]:
+            ops.grad_norm(st.grad, st.total, grad_scale, max_norm, self.norm_clip)
+        else:       # trainable gradients only, as clip_grad_norm_ sees them: the locked ranges are not read
+            if self._range_partials is None:
+                self._range_partials = torch.zeros(1024 * len(self.ranges), dtype=torch.float64, device=st.grad.device)
+            for k, (lo, hi) in enumerate(self.ranges):
+                ops.grad_sumsq_partial(st.grad[lo:hi], hi - lo, self._range_partials[1024 * k:1024 * (k + 1)])
+            ops.grad_norm_final(self._range_partials, self._range_partials.numel(), grad_scale, max_norm, self.norm_clip)
         return self.norm_clip
+
+    def _moments(self, k: int, lo: int, hi: int):
+        """Moment slices of flat[lo:hi], a piece of trainable range ``k``."""
+        a = self._moff[k] + lo - self.ranges[k][0]
+        return self.exp_avg[a:a + hi - lo], self.exp_avg_sq[a:a + hi - lo]
 
     def _step_sharded(self, grad_scale: float, max_norm: Optional[float]) -> torch.Tensor:
         g = self.param_groups[0]
@@ -104,20 +130,23 @@ class FusedAdamW:
         if self._behind is None:
             st = self.store
             size = max(64, (int(bucket_floats) + 63) // 64 * 64)
-            edges = list(range(0, st.total, size)) + [st.total]
-            if len(edges) > 2 and edges[-1] - edges[-2] < size // 2:
-                edges.pop(-2)
-            buckets = [(edges[k], edges[k + 1]) for k in range(len(edges) - 1)]
+            buckets, owner = [], []          # owner: the trainable range a bucket is a piece of
+            for r, (rlo, rhi) in enumerate(self.ranges):
+                edges = list(range(rlo, rhi, size)) + [rhi]
+                if len(edges) > 2 and edges[-1] - edges[-2] < size // 2:
+                    edges.pop(-2)
+                buckets += [(edges[k], edges[k + 1]) for k in range(len(edges) - 1)]
+                owner += [r] * (len(edges) - 1)
             first_second = min((sp.offset for sp in st.specs if not sp.name.startswith("visual.")), default=0)
-            k0 = next(k for k, (lo, hi) in enumerate(buckets) if lo <= first_second < hi)
+            k0 = next((k for k, (lo, hi) in enumerate(buckets) if hi > first_second), 0)
             order = list(range(k0, len(buckets))) + list(range(0, k0))
             pos = {k: i for i, k in enumerate(order)}
             copies = [[] for _ in buckets]
-            for c in st.copies.values():
+            for c in st.trainable_copies():      # a locked weight's copies were built once and never change
                 sp = st.by_name[c.name]
                 touched = [k for k, (lo, hi) in enumerate(buckets) if lo < sp.offset + sp.numel and sp.offset < hi]
                 copies[max(touched, key=lambda k: pos[k])].append(c)
-            self._behind = (buckets, order, copies, [st._transpose_plan(cs) for cs in copies])
+            self._behind = (buckets, order, copies, [st._transpose_plan(cs) for cs in copies], owner)
         return self._behind
 
     def _step_behind_forward(self, grad_scale: float, max_norm: Optional[float],
@@ -132,7 +161,7 @@ class FusedAdamW:
         st = self.store
         st.wait_all()               # a step without a forward in between: the previous update must be complete
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
-        buckets, order, copies, plans = self._behind_plan(int(os.environ.get("SC_ADAMW_BUCKET", 16 * 1024 * 1024)))
+        buckets, order, copies, plans, owner = self._behind_plan(int(os.environ.get("SC_ADAMW_BUCKET", 16 * 1024 * 1024)))
         cur = torch.cuda.current_stream(st.device)
         side = streams.comm_stream(st.device)       # (a low-priority stream of its own measured the same on ViT-B/16, worse on ViT-L/14)
         ready = torch.cuda.Event()
@@ -141,7 +170,8 @@ class FusedAdamW:
         with torch.cuda.stream(side):
             for k in order:
                 lo, hi = buckets[k]
-                ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], hi - lo, g["lr"],
+                m, v = self._moments(owner[k], lo, hi)
+                ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"],
                                g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip,
                                st.master_bf16[lo:hi])
                 st.refresh_range(lo, hi, copies[k], plans[k], fresh=(lo, hi))
@@ -175,8 +205,10 @@ class FusedAdamW:
         st = self.store
         st.wait_all()
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
-        ops.adamw_step_dev(st.master, st.grad, self.exp_avg, self.exp_avg_sq, st.total, self.hyper, g["betas"][0],
-                           g["betas"][1], g["eps"], g["weight_decay"], grad_scale, clip, st.master_bf16)
+        for k, (lo, hi) in enumerate(self.ranges):
+            m, v = self._moments(k, lo, hi)
+            ops.adamw_step_dev(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.hyper, g["betas"][0],
+                               g["betas"][1], g["eps"], g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -202,8 +234,10 @@ class FusedAdamW:
         if st.master.is_cuda and (behind == "1" or (behind not in ("0", "1") and st.total <= 200_000_000)):
             return self._step_behind_forward(grad_scale, max_norm, sumsq_partial)
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
-        ops.adamw_step(st.master, st.grad, self.exp_avg, self.exp_avg_sq, st.total, g["lr"], g["betas"][0],
-                       g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16)
+        for k, (lo, hi) in enumerate(self.ranges):
+            m, v = self._moments(k, lo, hi)
+            ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"], g["betas"][0],
+                           g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16[lo:hi])
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -213,8 +247,10 @@ class FusedAdamW:
         self.store.wait_all()           # an update may still be running behind the forward (communication stream)
         if self.exchange is not None:
             m, v = self.exchange.gather_moments(self.exp_avg), self.exchange.gather_moments(self.exp_avg_sq)
-        else:
+        elif self.ranges == [(0, self.store.total)]:
             m, v = self.exp_avg.clone(), self.exp_avg_sq.clone()
+        else:       # the full flat layout, zeros in the locked ranges: the file resumes with or without the lock
+            m, v = self._expand(self.exp_avg), self._expand(self.exp_avg_sq)
         return {"step": self.step_count, "exp_avg": m, "exp_avg_sq": v,
                 "param_groups": [{k: v_ for k, v_ in self.param_groups[0].items() if k != "params"}]}
 
@@ -231,9 +267,17 @@ class FusedAdamW:
         if self.exchange is not None:
             self.exchange.scatter_moments(m.to(self.exp_avg.device), self.exp_avg)
             self.exchange.scatter_moments(v.to(self.exp_avg.device), self.exp_avg_sq)
-        else:
-            self.exp_avg.copy_(m)
-            self.exp_avg_sq.copy_(v)
+        else:       # the trainable slices of the full layout
+            for k, (lo, hi) in enumerate(self.ranges):
+                dm, dv = self._moments(k, lo, hi)
+                dm.copy_(m[lo:hi])
+                dv.copy_(v[lo:hi])
+
+    def _expand(self, compact: torch.Tensor) -> torch.Tensor:
+        full = torch.zeros(self.store.total, dtype=compact.dtype, device=compact.device)
+        for k, (lo, hi) in enumerate(self.ranges):
+            full[lo:hi] = compact[self._moff[k]:self._moff[k] + hi - lo]
+        return full
 
 
 class GradAccumulator:
@@ -257,10 +301,18 @@ class GradAccumulator:
             self.acc = torch.zeros(self.store.total, dtype=torch.float32, device=self.store.grad.device)
         return self.acc
 
+    def _ranges(self) -> List[Tuple[int, int]]:
+        """The trainable ranges of the flat buffer (locked towers: nothing else is ever folded; the locked part of
+        ``store.grad`` holds zeros that no backward writes)."""
+        f = getattr(self.store, "trainable_ranges", None)
+        return list(f()) if f is not None else [(0, self.store.total)]
+
     def sumsq_partial(self) -> torch.Tensor:
-        """The 1024-slot fp64 buffer to pass as ``fold(..., partial=)`` and then as ``FusedAdamW.step(sumsq_partial=)``."""
-        if self.partial is None:
-            self.partial = torch.zeros(1024, dtype=torch.float64, device=self.store.grad.device)
+        """The fp64 buffer (1024 slots per trainable range: 1024 without a lock) to pass as ``fold(..., partial=)`` and then
+        as ``FusedAdamW.step(sumsq_partial=)``."""
+        n = 1024 * len(self._ranges())
+        if self.partial is None or self.partial.numel() != n:
+            self.partial = torch.zeros(n, dtype=torch.float64, device=self.store.grad.device)
         return self.partial
 
     def fold(self, first: bool, last: bool, lo: int = 0, hi: Optional[int] = None, partial: Optional[torch.Tensor] = None) -> None:
@@ -275,6 +327,18 @@ class GradAccumulator:
             raise ValueError("GradAccumulator.fold: partial= needs the whole buffer of a group's last micro-batch")
         if hi == lo:
             return
+        ranges = self._ranges()
+        if ranges != [(0, self.store.total)]:      # locked towers: the pieces of [lo, hi) that hold trainable gradients
+            from .lock import intersect
+            if partial is not None and partial.numel() != 1024 * len(ranges):
+                raise ValueError("GradAccumulator.fold: partial= must come from sumsq_partial() (1024 slots per trainable range)")
+            for k, (a, b) in enumerate(ranges):
+                for x, y in intersect([(a, b)], lo, hi):
+                    self._fold_piece(first, last, x, y, None if partial is None else partial[1024 * k:1024 * (k + 1)])
+            return
+        self._fold_piece(first, last, lo, hi, partial)
+
+    def _fold_piece(self, first: bool, last: bool, lo: int, hi: int, partial: Optional[torch.Tensor]) -> None:
         g = self.store.grad
         if last:
             acc = None if first else self._acc()[lo:hi]

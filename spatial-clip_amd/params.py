@@ -140,7 +140,10 @@ def _dist_world() -> int:
 
 
 class ParamStore:
-    def __init__(self, cfg: ModelCfg, device: torch.device, seed: int = 0, fp8: bool = False, shard_world: Optional[int] = None):
+    def __init__(self, cfg: ModelCfg, device: torch.device, seed: int = 0, fp8: bool = False, shard_world: Optional[int] = None,
+                 init: bool = True):
+        """``init=False``: lay the buffers out and stop before the first kernel launch (values and compute copies stay zero) --
+        what the host-side tests of the layout, the locks and the optimiser state need, on any device."""
         self.cfg = cfg
         self.device = device
         self.fp8 = fp8          # forward GEMMs of the transformer blocks in e4m3 (BASELINE configs[4]); see csrc/sc_fp8.hip
@@ -168,7 +171,12 @@ class ParamStore:
             self.params[s.name] = p
         self.copies: Dict[str, LinearCopy] = {}
         self._build_copies()
-        self.init_parameters(seed)
+        # locked towers (LiT; lock()): names of the parameters no optimiser step may touch, and whether an optimiser has
+        # already laid its state out for the current set (FusedAdamW sets it; lock() then refuses)
+        self.locked: set = set()
+        self.optimizer_built = False
+        if init:
+            self.init_parameters(seed)
 
     # ------------------------------------------------------------------ views
     def p(self, name: str) -> torch.Tensor:
@@ -233,6 +241,51 @@ class ParamStore:
 
     def num_parameters(self) -> int:
         return sum(s.numel for s in self.specs)
+
+    # ------------------------------------------------------------------ locked parameters (LiT)
+    def lock(self, names) -> None:
+        """Make ``names`` the locked parameters of their tower (the caller passes a whole tower's locked set; earlier locks of
+        OTHER names stay): ``requires_grad=False`` and no ``.grad`` on their nn.Parameter views, as a frozen parameter of the
+        reference has, and the locked part of the flat gradient buffer zeroed once -- no backward writes there afterwards."""
+        if self.optimizer_built:
+            raise RuntimeError("lock: an optimiser was already built for this net (its moments and launch plan cover the "
+                               "trainable floats of that moment); lock the towers first, then build the optimiser")
+        self.wait_all()
+        for n in names:
+            sp = self.by_name[n]
+            self.locked.add(n)
+            self.params[n].requires_grad_(False)
+            self.params[n].grad = None
+            self.grad[sp.offset:sp.offset + _round_up(max(sp.numel, 1), ALIGN)].zero_()
+        self._tp_plan_trainable = False
+
+    def unlock(self, names) -> None:
+        """Inverse of ``lock`` for ``names`` (a tower locked again with more unlocked groups)."""
+        if self.optimizer_built:
+            raise RuntimeError("unlock: an optimiser was already built for this net")
+        for n in names:
+            if n in self.locked:
+                self.locked.discard(n)
+                self.params[n].requires_grad_(True)
+                self.params[n].grad = self.g(n)
+        self._tp_plan_trainable = False
+
+    def trainable_names(self) -> List[str]:
+        return [s.name for s in self.specs if s.name not in self.locked]
+
+    def trainable_ranges(self) -> List[Tuple[int, int]]:
+        """Merged, sorted (lo, hi) ranges of the flat buffers that hold trainable parameters.  Spec offsets are ALIGN-float
+        aligned, so every range is; the last one takes the zero padding behind the last parameter, so a net without locks has
+        the one range (0, total)."""
+        from .lock import merge_ranges
+        return merge_ranges(self.specs, self.locked, self.total, ALIGN)
+
+    def trainable_floats(self) -> int:
+        return sum(hi - lo for lo, hi in self.trainable_ranges())
+
+    def trainable_copies(self) -> List[LinearCopy]:
+        """The Linear weights an optimiser step changes: only their derived copies are refreshed after it."""
+        return [c for c in self.copies.values() if c.name not in self.locked]
 
     # ------------------------------------------------------------------ init / state dict
     @torch.no_grad()
@@ -412,6 +465,13 @@ class ParamStore:
         self.wait_all()
         if not mirror_is_fresh:
             ops.cast_pad_bf16(self.master.view(1, -1), self.master_bf16.view(1, -1), 1, self.total, self.total)
+        if mirror_is_fresh and self.locked:
+            # after an optimiser step: the weights of a locked range have not changed since their copies were built
+            copies = self.trainable_copies()
+            if getattr(self, "_tp_plan_trainable", False) is False:
+                self._tp_plan_trainable = self._transpose_plan(copies)
+            self._refresh_copies(copies, self._tp_plan_trainable)
+            return
         if getattr(self, "_tp_plan", False) is False:
             self._tp_plan = self._transpose_plan(list(self.copies.values()))
         self._refresh_copies(list(self.copies.values()), self._tp_plan)

@@ -379,6 +379,13 @@ class TransformerStack:
         self._side: Optional[torch.cuda.Stream] = None      # ONE weight-gradient side stream per stack, created on first use
         self._trials: Dict[tuple, OverlapTrial] = {}        # SC_OVERLAP=auto: (B, L) -> trial
         self._zero_bias_set = False
+        # locked tower (lock.TowerLock): index of the first trainable block.  The blocks below it run their forward as ever but
+        # keep nothing per block (their buffers rotate between two sets) and the backward stops after block ``floor``
+        self.floor = 0
+
+    def _tag(self, i: int) -> str:
+        """Buffer-name tag of block ``i``: its index, or one of two rotating sets for a locked block."""
+        return f"lk{i & 1}" if i < self.floor else str(i)
 
     @property
     def r16(self) -> bool:
@@ -411,6 +418,8 @@ class TransformerStack:
     def _act(self, kind: str, i: int, shape) -> torch.Tensor:
         """Buffer of a block's recomputable activation (a1 / a2 / h): one per block, or two rotating ones in
         recomputation mode (the CLS-only last block keeps its own: it runs first in the backward, nothing to rebuild)."""
+        if i < self.floor:
+            return self.bufs.get(f"{kind}.lk{i & 1}", shape, BF16)
         if self.recompute and not (self.cls_only_last and i == self.layers - 1):
             return self.bufs.get(f"{kind}.rc{i & 1}", shape, BF16)
         return self.bufs.get(f"{kind}.{i}", shape, BF16)
@@ -449,7 +458,8 @@ class TransformerStack:
 
     def _stats(self, k: int, i: int, rows: int):
         """(mean, rstd) buffers of LayerNorm ``k`` (1 or 2) of block ``i``."""
-        return self.bufs.get(f"m{k}.{i}", (rows,), F32), self.bufs.get(f"r{k}.{i}", (rows,), F32)
+        t = self._tag(i)
+        return self.bufs.get(f"m{k}.{t}", (rows,), F32), self.bufs.get(f"r{k}.{t}", (rows,), F32)
 
     def layer_param_names(self, i: int) -> List[str]:
         leaves = ["ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
@@ -475,11 +485,25 @@ class TransformerStack:
         # pieces anyway) and the c_proj data gradient becomes one multiply; recomputation mode keeps u, from which it rebuilds
         # h = gelu(u)
         p = self.fwd = StackPass(B, L, M, r16, w8, u_holds_grad=not self.recompute, x_in=[None] * self.layers)
+        if self.floor >= 2:
+            self._reserve_locked_sets(p)
         for i in range(self.layers):
             s.wait_names(self.layer_param_names(i))      # sharded optimiser: this block's refreshed weights have landed (no-op otherwise)
             p.x_in[i] = x
             x = self._block_fwd(i, x, p)
         return x
+
+    def _reserve_locked_sets(self, p: StackPass) -> None:
+        """Both rotating buffer sets of a locked prefix, whole, whatever the blocks will touch (a class-token-only last block
+        leaves the MLP part of its set unused): the activation memory of the prefix is the same at every depth."""
+        bf, d, mlp, M = self.bufs, self.d, self.mlp, p.M
+        XD = BF16 if p.r16 else F32
+        for t in ("lk0", "lk1"):
+            for kind, shape, dt in (("a1", (M, d), BF16), ("a2", (M, d), BF16), ("h", (M, mlp), BF16), ("qkv", (M, 3 * d), BF16),
+                                    ("o", (M, d), BF16), ("u", (M, mlp), BF16), ("xmid", (M, d), XD), ("xout", (M, d), XD),
+                                    ("lse", (p.B, self.H, p.L), F32), ("m1", (M,), F32), ("r1", (M,), F32), ("m2", (M,), F32),
+                                    ("r2", (M,), F32)):
+                bf.get(f"{kind}.{t}", shape, dt)
 
     def _block_fwd(self, i: int, x: torch.Tensor, p: StackPass) -> torch.Tensor:
         s, d, mlp, bf, B, L, M = self.s, self.d, self.mlp, self.bufs, p.B, p.L, p.M
@@ -489,7 +513,8 @@ class TransformerStack:
         qa = self._q8("a", M, d)            # fp8: LayerNorm also emits the e4m3 copy + row scales (rotating scratch)
         ops.layernorm_fwd(x, s.p(self._n(i, "ln_1.weight")), s.p(self._n(i, "ln_1.bias")), a1, *self._stats(1, i, M), M, d,
                           q8=qa and qa[0], q8_scale_inv=qa and qa[1])
-        qkv = bf.get(f"qkv.{i}", (M, 3 * d), BF16)
+        tg = self._tag(i)
+        qkv = bf.get(f"qkv.{tg}", (M, 3 * d), BF16)
         last_cls = self.cls_only_last and i == self.layers - 1
         p.q_cls_only = last_cls and self._q_dead_ok(qa, i)
         if p.q_cls_only:
@@ -503,12 +528,12 @@ class TransformerStack:
         else:
             self._linear_fwd(ops.EPI_BF16_BIAS, a1, self._n(i, "attn.in_proj_weight"), qkv,
                              M=M, N=3 * d, K=d, bias=s.p(self._n(i, "attn.in_proj_bias")), q8=qa)
-        o = bf.get(f"o.{i}", (M, d), BF16)
-        lse = bf.get(f"lse.{i}", (B, self.H, L), F32)
+        o = bf.get(f"o.{tg}", (M, d), BF16)
+        lse = bf.get(f"lse.{tg}", (B, self.H, L), F32)
         if last_cls:
             return self._forward_last_cls(i, x, qkv, o, lse, p)
         ops.attn_fwd(qkv, B, L, self.H, self.dh, self.causal, out=o, lse=lse)
-        xmid = bf.get(f"xmid.{i}", (M, d), XD)
+        xmid = bf.get(f"xmid.{tg}", (M, d), XD)
         self._linear_fwd(epi_res, o, self._n(i, "attn.out_proj.weight"), xmid,
                          M=M, N=d, K=d, bias=s.p(self._n(i, "attn.out_proj.bias")), res=x)
         a2 = self._act("a2", i, (M, d))
@@ -518,7 +543,7 @@ class TransformerStack:
             t8a = (bf.get(f"t8.a2.{i}", (M, d), torch.uint8), sc, amax)
         ops.layernorm_fwd(xmid, s.p(self._n(i, "ln_2.weight")), s.p(self._n(i, "ln_2.bias")), a2, *self._stats(2, i, M), M, d,
                           q8=qa and qa[0], q8_scale_inv=qa and qa[1], t8=t8a)
-        u = bf.get(f"u.{i}", (M, mlp), BF16)
+        u = bf.get(f"u.{tg}", (M, mlp), BF16)
         h = self._act("h", i, (M, mlp))
         hq = None
         if self.fp8 and self._dq_on and self.fp8_train_pass:      # the GELU epilogue also emits e4m3(h) with last step's scale + records max|h|
@@ -527,7 +552,7 @@ class TransformerStack:
             hq = dict(q8_out=h8, q8_scale=h_scale, q8_amax=h_amax)
         self._linear_fwd(self.epi_grad_pair if p.u_holds_grad else self.epi_pair, a2, self._n(i, "mlp.c_fc.weight"), u,
                          M=M, N=mlp, K=d, bias=s.p(self._n(i, "mlp.c_fc.bias")), out2=h, q8=qa, **(hq or {}))
-        xo = bf.get(f"xout.{i}", (M, d), XD)
+        xo = bf.get(f"xout.{tg}", (M, d), XD)
         cpj = s.copies[self._n(i, "mlp.c_proj.weight")]
         if hq is not None and self.scales.ready and cpj.w8 is not None:
             ops.gemm_fp8(epi_res, h8, h_scale_inv, cpj.w8, cpj.w8s, xo, M=M, N=d,
@@ -607,7 +632,7 @@ class TransformerStack:
         else:
             ops.gemm(ops.NT, ops.EPI_BF16, dqkv, wb, c.dA, M=M, N=d, K=3 * d)
         dres_bf = bf.get("dres_bf.0", (M, d), BF16)
-        prev_bias = s.g(self._n(i - 1, "mlp.c_proj.bias")) if i > 0 else None
+        prev_bias = s.g(self._n(i - 1, "mlp.c_proj.bias")) if i > self.floor else None    # block i - 1 locked: no gradient of its bias
         qg = p.g_q8 = self._q8("g", M, d)
         t8g = None
         if p.w8 and i > 0 and qg is not None and _res_grad_bf16():     # per-tensor e4m3 copy: dY of block i - 1's c_proj weight gradient
@@ -678,7 +703,7 @@ class TransformerStack:
                 sched.run(lambda: on_layer_done(top))
         c.ring = GradRing([dres_bf, bf.get("dres_bf.1", (M, d), BF16), bf.get("dres_bf.2", (M, d), BF16)],
                           [bf.get(f"t8.g.{k}", (M, d), torch.uint8) for k in range(3)] if c.w8 else None)
-        for i in reversed(range(top)):
+        for i in reversed(range(self.floor, top)):     # a locked tower's backward stops after its first trainable block
             if i == self.layers - 1 and not last_bias_colsum_done:
                 ops.colsum_bf16(c.ring.current[0], M, d, self.s.g(self._n(i, "mlp.c_proj.bias")))
             mlp_wgrads = self._mlp_bwd(i, c)
@@ -794,7 +819,7 @@ class TransformerStack:
             sched.run(lambda: launch_wgrads(probs, M, "attn", c.wg_mode), reads)
         ops.gemm(ops.NT, ops.EPI_BF16, dqkv, s.copies[self._n(i, "attn.in_proj_weight")].wb, c.dA, M=M, N=d, K=3 * d)
         # LN1 backward; its column sum is the previous block's c_proj.bias gradient
-        prev_bias = s.g(self._n(i - 1, "mlp.c_proj.bias")) if i > 0 else None
+        prev_bias = s.g(self._n(i - 1, "mlp.c_proj.bias")) if i > self.floor else None    # block i - 1 locked: no gradient of its bias
         g2, g2_8 = c.ring.advance()
         sched.before_write(g2)
         t8n = None

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .model_configs import ModelCfg
+from .lock import TowerLock
 from .params import ParamStore
 from .stack import BF16, F32, TransformerStack, _Bufs, _res_stream_bf16, _splitk_for  # noqa: F401  (re-exported)
 
@@ -44,16 +45,25 @@ def _proj_fwd(t, pooled: torch.Tensor) -> torch.Tensor:
     return t.f
 
 
-def _head_bwd(t, d_f: torch.Tensor) -> torch.Tensor:
-    """Backward of ``_head_fwd`` down to the final LayerNorm's output: writes the projection's gradient, returns d(pooled)."""
+def _head_bwd(t, d_f: torch.Tensor, dgrad: bool = True) -> Optional[torch.Tensor]:
+    """Backward of ``_head_fwd`` down to the final LayerNorm's output: writes the projection's gradient, returns d(pooled).
+    ``dgrad=False`` (a locked tower whose projection alone is trainable): the weight gradient only, returns None."""
     s, bf, B, d, D = t.s, t.bufs, t.B, t.d, t.D
     proj = t.param_names_head()[2]
     d_raw = bf.get("d_raw", (B, D), BF16)
     ops.l2norm_bwd(d_f.contiguous().float(), t.f, bf.get("inv", (B,), F32), d_raw, B, D)
-    d_pooled = bf.get("d_pooled", (B, d), BF16)
-    ops.gemm(ops.NT, ops.EPI_BF16, d_raw, s.copies[proj].wb, d_pooled, M=B, N=d, K=D)
+    d_pooled = None
+    if dgrad:
+        d_pooled = bf.get("d_pooled", (B, d), BF16)
+        ops.gemm(ops.NT, ops.EPI_BF16, d_raw, s.copies[proj].wb, d_pooled, M=B, N=d, K=D)
     ops.gemm(ops.TN, ops.EPI_F32, bf.get("pooled", (B, d), BF16), d_raw, s.g(proj), M=d, N=D, K=B)
     return d_pooled
+
+
+def _set_lock(t, unlocked: Optional[int]) -> None:
+    """Give tower ``t`` (with a ``stack`` of ``layers`` blocks) the lock ``unlocked`` (None: not locked)."""
+    t.lock = TowerLock(t.stack.layers, unlocked)
+    t.stack.floor = t.lock.floor
 
 
 class PatchTransformerTower:
@@ -93,6 +103,10 @@ class PatchTransformerTower:
         self.L_run = tokens
         self._keep = (None, None)
         self._pad_zeroed: Dict[str, torch.Tensor] = {}      # patch buffer name -> the tensor whose K padding is zeroed
+        self.lock = TowerLock(layers)       # LiT: nothing locked (SpatialClipNet.lock_image_tower -> set_lock)
+
+    def set_lock(self, unlocked: Optional[int]) -> None:
+        _set_lock(self, unlocked)
 
     def _n(self, leaf: str) -> str:
         return self.prefix + leaf
@@ -172,6 +186,11 @@ class PatchTransformerTower:
         self._name_pass_bufs()
         M, Mp = B * L, B * (L - 1)
         bf = self.bufs
+        if self.lock.head_only:         # locked up to the projection: the backward is that one weight gradient
+            _head_bwd(self, d_f, dgrad=False)
+            if on_bucket is not None:
+                on_bucket(self.param_names_head()[2:])
+            return
         d_pooled = _head_bwd(self, d_f)
         head_bwd = self._head_bwd_avg if self.pool_type == "avg" else self._head_bwd_tok
         dres, dres_bf = head_bwd(d_pooled, B, L)
@@ -179,6 +198,8 @@ class PatchTransformerTower:
             on_bucket(self.param_names_head())
         cb = (lambda i: on_bucket(self.stack.layer_param_names(i))) if on_bucket is not None else None
         dres = self.stack.backward(dres, dres_bf, last_bias_colsum_done=True, on_layer_done=cb)
+        if not self.lock.stem:          # locked stem: nothing below the floor block has a gradient
+            return
         # stem: ln_pre / positional / class embedding / patch embedding (no gradient flows to the input)
         dpatch = bf.get("dpatch", (Mp, d), BF16)
         if self.no_ln_pre:
@@ -424,6 +445,10 @@ class TextTower:
         if self.pool_type not in ("argmax", "last", "first"):
             raise ValueError(f"text pool_type {self.pool_type!r}: 'argmax', 'last' or 'first'")
         self._eot_filled: Optional[torch.Tensor] = None
+        self.lock = TowerLock(t.layers)     # LiT: nothing locked (SpatialClipNet.lock_text_tower -> set_lock)
+
+    def set_lock(self, unlocked: Optional[int]) -> None:
+        _set_lock(self, unlocked)
 
     def param_names_head(self) -> List[str]:
         return ["ln_final.weight", "ln_final.bias", "text_projection"]
@@ -462,6 +487,11 @@ class TextTower:
         s, d, L, B = self.s, self.d, self.L, self.B
         M = B * L
         bf = self.bufs
+        if self.lock.head_only:         # locked up to text_projection: the backward is that one weight gradient
+            _head_bwd(self, d_f, dgrad=False)
+            if on_bucket is not None:
+                on_bucket(self.param_names_head()[2:])
+            return
         d_pooled = _head_bwd(self, d_f)
         dxe = bf.get("dx_eot", (B, d), F32)
         last = self.t.layers - 1
@@ -478,6 +508,8 @@ class TextTower:
             on_bucket(self.param_names_head())
         cb = (lambda i: on_bucket(self.stack.layer_param_names(i))) if on_bucket is not None else None
         self.stack.backward(dres, dres_bf, last_bias_colsum_done=True, on_layer_done=cb)
+        if not self.lock.stem:          # locked embeddings: nothing below the floor block has a gradient
+            return
         # scatter-add of the embedding gather: bit-reproducible by default (SC_EMBED_BWD_ATOMIC=1: the float-atomic kernel, A/B)
         ops.token_embed_bwd(self.text, dres, s.g("token_embedding.weight"), s.g("positional_embedding"), B, L, d, self.V,
                             eot=bf.get("eot", (B,), torch.int32) if self.stack.causal else None, deterministic=os.environ.get("SC_EMBED_BWD_ATOMIC", "0") != "1")
