@@ -489,6 +489,19 @@ int sc_adamw_hyper_host(float lr, float beta1, float beta2, int step, float* out
 int sc_adamw_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                       const float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                       const float* norm_clip, void* params_bf16, void* stream);
+/* Parameter groups (an optimiser built from a list of groups: per-group lr and weight decay; open_clip's no-decay rule,
+ * src/open_clip_train/main.py:340-352).  The flat buffers are laid out in 64-float slots that no two parameters share;
+ * chunk_group[n / 64] (DEVICE bytes) names the group of each slot of THIS range and ONE streaming launch updates the range,
+ * whatever the interleaving of the groups.  group_hyper (DEVICE, 2 + 2 * n_groups floats) = {1 - beta1^step,
+ * sqrt(1 - beta2^step)}, then {lr_g, wd_g} per group: sc_adamw_groups_hyper_host fills a HOST copy of it (the bias
+ * corrections with sc_adamw_step's expressions) for the small copy in front of the launch, which is therefore the same
+ * for the eager and the graph-captured step.  Every slot of group g gets the bits of sc_adamw_step run on it with
+ * (lr_g, wd_g).  n: a positive multiple of 64; 1 <= n_groups <= 256; table entries < n_groups are the caller's duty. */
+int sc_adamw_groups_hyper_host(const float* lr, const float* wd, int n_groups, float beta1, float beta2, int step,
+                               float* out_host);
+int sc_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                         const unsigned char* chunk_group, const float* group_hyper, int n_groups, float beta1, float beta2,
+                         float eps, float grad_scale, const float* norm_clip, void* params_bf16, void* stream);
 /* The two halves of sc_grad_norm for an optimiser that owns 1/W of every gradient bucket (reduce-scatter ->
  * AdamW on the rank's shard -> all-gather; Lightning's DDP mean, configs/trainer/ddp.yaml:4, replaced): 1024 fp64 partial
  * sums of squares per contiguous piece of the shard, then -- after the caller has all-reduced (SUM) the concatenated

@@ -89,6 +89,60 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---- parameter groups (per-group lr / weight decay, torch.optim's list-of-dicts form): the same streaming update, ONE
+// launch per range, with the two scalars that depend on the group looked up per 64-float slot.  The flat buffers are laid
+// out in 64-float slots and no two parameters share one (params.py ALIGN), so float4 i belongs to slot i >> 4: sixteen
+// consecutive lanes read the same table byte (one byte per 768 bytes of traffic) and the same LDS pair (a broadcast read).
+//   hyper (DEVICE) = {1 - b1^t, sqrt(1 - b2^t)}, then {lr_g, wd_g} per group
+// decay and step are formed per group at block start with adamw_kernel's expressions, and the loop body is adamw_kernel's,
+// expression for expression: under -ffp-contract=fast the same source shape gets the same contractions, so a slot of group
+// g comes out with the bits of adamw_kernel run on it with (lr_g, wd_g).  The table entries are validated where the table
+// is built (optim.FusedAdamW); any byte indexes inside the 256 LDS pairs.
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long long n,
+                                                           const unsigned char* __restrict__ chunk_group,
+                                                           const float* __restrict__ hyper, int n_groups, float b1, float b2,
+                                                           float eps, float gscale, const float* __restrict__ normclip,
+                                                           bf16* __restrict__ pbf) {
+    __shared__ float2 group_scalars[256];       // {decay, step} of each group
+    const float bc1 = hyper[0], bc2_sqrt = hyper[1];
+    if ((int)threadIdx.x < n_groups) {
+        const float lr = hyper[2 + 2 * threadIdx.x], wd = hyper[3 + 2 * threadIdx.x];
+        const float decay = 1.0f - lr * wd;
+        const float step = lr / bc1;
+        group_scalars[threadIdx.x] = make_float2(decay, step);
+    }
+    __syncthreads();
+    const float gs = gscale * (normclip ? normclip[1] : 1.0f);
+    const long long n4 = n >> 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (long long)gridDim.x * blockDim.x) {
+        const float2 ds = group_scalars[chunk_group[i >> 4]];
+        const float decay = ds.x, step = ds.y;
+        f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float ge = gg[c] * gs;
+            pp[c] *= decay;
+            mm[c] = b1 * mm[c] + (1.0f - b1) * ge;
+            vv[c] = b2 * vv[c] + (1.0f - b2) * ge * ge;
+            const float denom = sqrtf(vv[c]) / bc2_sqrt + eps;
+            pp[c] -= step * (mm[c] / denom);
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pp;
+        if (pbf) {
+            bf16x4 o;
+            o[0] = (bf16)pp[0]; o[1] = (bf16)pp[1]; o[2] = (bf16)pp[2]; o[3] = (bf16)pp[3];
+            reinterpret_cast<bf16x4*>(pbf)[i] = o;
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mm;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+}
+
 // ---- gradient accumulation (Trainer accumulate_grad_batches): every backward OVERWRITES the flat gradient buffer, so the
 // sum over the micro-batches of a group is a running fp32 buffer beside it, folded once per micro-batch by this kernel:
 //   mode 0 (first)  acc   = scale * grads
@@ -283,6 +337,41 @@ extern "C" int sc_adamw_step_dev(float* params, const float* grads, float* exp_a
     adamw_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps,
                                                            weight_decay, 1.f, 1.f, grad_scale, norm_clip, (bf16*)params_bf16,
                                                            hyper);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// Parameter groups: host-side scalars of one step, {1 - beta1^step, sqrt(1 - beta2^step)} (the bits sc_adamw_step forms) and
+// then {lr_g, wd_g} per group, for the small pinned -> device copy in front of sc_adamw_step_groups.
+extern "C" int sc_adamw_groups_hyper_host(const float* lr, const float* wd, int n_groups, float beta1, float beta2, int step,
+                                          float* out_host) {
+    SC_CHECK(lr != nullptr && wd != nullptr && out_host != nullptr, "sc_adamw_groups_hyper_host: lr, wd and the host output are required");
+    SC_CHECK(n_groups >= 1 && n_groups <= 256, "sc_adamw_groups_hyper_host: n_groups = %d (1 .. 256)", n_groups);
+    SC_CHECK(step >= 1, "sc_adamw_groups_hyper_host: step = %d (>= 1)", step);
+    adamw_bias_corrections(beta1, beta2, step, out_host, out_host + 1);
+    for (int k = 0; k < n_groups; ++k) {
+        out_host[2 + 2 * k] = lr[k];
+        out_host[3 + 2 * k] = wd[k];
+    }
+    return 0;
+}
+
+// AdamW over one range of the flat buffers with per-group lr / weight decay: chunk_group[n / 64] (DEVICE bytes) names the
+// group of each 64-float slot of THIS range, group_hyper (DEVICE, 2 + 2 * n_groups floats) comes from
+// sc_adamw_groups_hyper_host.  One launch form for the eager and the graph-captured step.
+extern "C" int sc_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                                    const unsigned char* chunk_group, const float* group_hyper, int n_groups, float beta1,
+                                    float beta2, float eps, float grad_scale, const float* norm_clip, void* params_bf16,
+                                    void* stream) {
+    SC_CHECK(n > 0 && (n % 64) == 0, "sc_adamw_step_groups: n = %lld must be a positive multiple of 64 (whole slots)", n);
+    SC_CHECK(n_groups >= 1 && n_groups <= 256, "sc_adamw_step_groups: n_groups = %d (1 .. 256)", n_groups);
+    SC_CHECK(chunk_group != nullptr && group_hyper != nullptr, "sc_adamw_step_groups: chunk_group and group_hyper are required");
+    SC_CHECK(params && grads && exp_avg && exp_avg_sq, "sc_adamw_step_groups: params, grads and both moments are required");
+    long long nb = (n / 4 + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    adamw_groups_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, chunk_group, group_hyper,
+                                                                  n_groups, beta1, beta2, eps, grad_scale, norm_clip,
+                                                                  (bf16*)params_bf16);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -97,8 +97,13 @@ class SpatialClipLitModule(torch.nn.Module):
     def __init__(self, net: SpatialClipNet, loss_fn: torch.nn.Module, optimizer_cfg: Callable, scheduler_cfg: Callable,
                  train_metrics: Optional[ContrastiveMetrics] = None, val_metrics: Optional[ContrastiveMetrics] = None,
                  test_metrics: Optional[ContrastiveMetrics] = None, global_hvg_path: Optional[str] = None,
-                 dist_net: Optional[SpatialClipNet] = None):
+                 dist_net: Optional[SpatialClipNet] = None, param_groups: Any = None):
         super().__init__()
+        # optimiser parameter groups (config key model.param_groups): None -- the reference's un-grouped
+        # optimizer_cfg(params=self.parameters()); a mapping {"no_decay": "open_clip" | None, "lr_scale": {prefix: factor}};
+        # or a callable (net) -> list of group dicts.  Checked here, so that a bad key fails before anything trains.
+        from . import optim
+        self.param_groups = optim.check_param_groups_cfg(param_groups)
         # distillation teacher (open_clip --distill-model / --distill-pretrained): frozen, evaluated under no_grad on the
         # student's batch.  Kept OUT of the module tree (a tuple is not a submodule): parameters(), state_dict(), checkpoints,
         # the optimiser and the DDP gradient exchange see the student alone, and module.train() cannot take it out of eval().
@@ -281,8 +286,32 @@ class SpatialClipLitModule(torch.nn.Module):
         self.log_dict(self.test_metrics, on_step=False, on_epoch=True, sync_dist=True)
         self._zero_shot_update(batch, output, "test/zero_shot_pcc")
 
+    def optimizer_param_groups(self):
+        """The group dicts ``param_groups`` asks for.  The base learning rate and weight decay are the ones ``optimizer_cfg``
+        will build the optimiser with: its bound keywords (a ``functools.partial``, as Hydra's ``_partial_`` gives), else the
+        defaults of its signature."""
+        from . import optim
+        if callable(self.param_groups):
+            return list(self.param_groups(self.net))
+        cfg = self.hparams.optimizer_cfg
+
+        def bound(key):
+            keywords = getattr(cfg, "keywords", None) or {}
+            if key in keywords:
+                return keywords[key]
+            par = inspect.signature(getattr(cfg, "func", cfg)).parameters.get(key)
+            if par is None or par.default is inspect.Parameter.empty:
+                raise ValueError(f"param_groups: optimizer_cfg neither binds {key!r} nor has a default for it, and the groups "
+                                 "are scaled from it")
+            return par.default
+        return optim.build_param_groups(self.net, self.param_groups, lr=float(bound("lr")),
+                                        weight_decay=float(bound("weight_decay")))
+
     def configure_optimizers(self) -> Dict[str, Any]:
-        optimizer = self.hparams.optimizer_cfg(params=self.parameters())
+        if self.param_groups is None:
+            optimizer = self.hparams.optimizer_cfg(params=self.parameters())
+        else:
+            optimizer = self.hparams.optimizer_cfg(params=self.optimizer_param_groups())
         if self.trainer is None:
             return {"optimizer": optimizer}
         if self.trainer.max_steps == -1:

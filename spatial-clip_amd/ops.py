@@ -813,6 +813,47 @@ def adamw_step_dev(p, g, m, v, n, hyper, beta1, beta2, eps, wd, grad_scale, norm
                                        _stream()), "sc_adamw_step_dev")
 
 
+def adamw_groups_hyper_host(lr, wd, beta1, beta2, step, out_host):
+    """Fill the HOST fp32 tensor ``out_host`` (2 + 2 * len(lr) floats, pinned for an async copy) with
+    {1 - beta1^step, sqrt(1 - beta2^step)} and then {lr_g, wd_g} per group: what ``adamw_step_groups`` reads from its device
+    copy.  The bias corrections are formed by the library with ``sc_adamw_step``'s expressions."""
+    n_groups = len(lr)
+    if len(wd) != n_groups:
+        raise ValueError(f"adamw_groups_hyper_host: {n_groups} learning rates, {len(wd)} weight decays")
+    if out_host.is_cuda or out_host.dtype != torch.float32 or not out_host.is_contiguous() or out_host.numel() < 2 + 2 * n_groups:
+        raise ValueError(f"adamw_groups_hyper_host: out_host must be {2 + 2 * n_groups} contiguous float32 in host memory")
+    arr = ctypes.c_float * max(n_groups, 1)
+    check(_lib.lib().sc_adamw_groups_hyper_host(arr(*[float(x) for x in lr]), arr(*[float(x) for x in wd]), n_groups,
+                                                float(beta1), float(beta2), int(step), out_host.data_ptr()),
+          "sc_adamw_groups_hyper_host")
+    return out_host
+
+
+def adamw_step_groups(p, g, m, v, n, chunk_group, group_hyper, n_groups, beta1, beta2, eps, grad_scale, norm_clip, p_bf16=None):
+    """AdamW over one range of the flat buffers with per-group lr / weight decay, one launch: ``chunk_group`` (uint8, device)
+    names the group of each 64-float slot of the range, ``group_hyper`` (fp32, device) is ``adamw_groups_hyper_host``'s
+    layout.  ``None`` for either is passed on as NULL, which the library refuses."""
+    n, n_groups = int(n), int(n_groups)
+    if chunk_group is not None:
+        _req(chunk_group, torch.uint8, "chunk_group")
+        if n > 0 and chunk_group.numel() < n // 64:
+            raise ValueError(f"adamw_step_groups: chunk_group holds {chunk_group.numel()} slots, the range has {n // 64}")
+    if group_hyper is not None:
+        _req(group_hyper, torch.float32, "group_hyper")
+        if 1 <= n_groups <= 256 and group_hyper.numel() < 2 + 2 * n_groups:
+            raise ValueError(f"adamw_step_groups: group_hyper holds {group_hyper.numel()} floats, {n_groups} groups need "
+                             f"{2 + 2 * n_groups}")
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"adamw_step_groups: {name} holds {t.numel()} floats, n = {n}")
+    if p_bf16 is not None and p_bf16.numel() < n:
+        raise ValueError(f"adamw_step_groups: the bf16 mirror holds {p_bf16.numel()} elements, n = {n}")
+    check(_lib.lib().sc_adamw_step_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, _ptr(chunk_group),
+                                          _ptr(group_hyper), n_groups, float(beta1), float(beta2), float(eps), float(grad_scale),
+                                          _ptr(norm_clip), _ptr(p_bf16), _stream()), "sc_adamw_step_groups")
+
+
 def cast_transpose_batched(master, desc, tile_prefix, n, total_tiles, mirror_bf16=None):
     check(_lib.lib().sc_cast_transpose_batched(master.data_ptr(), _ptr(mirror_bf16), desc.data_ptr(),
                                                tile_prefix.data_ptr(), n, total_tiles, _stream()),

@@ -4,13 +4,16 @@
 (configs/optimizer/adamw.yaml) and applies one fused kernel over the flat fp32 buffers of the ParamStore: global
 grad-norm clip (Lightning ``gradient_clip_val``), DDP's 1/world_size mean, decoupled weight decay on ALL
 parameters (the reference passes ``self.parameters()`` un-grouped, src/models/spatial_clip_module.py:139) and the
-bf16 compute-copy refresh.  ``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
+bf16 compute-copy refresh.  ``params`` may also be torch's other form, a list of ``{"params": [...], "lr": ...,
+"weight_decay": ...}`` dicts (``open_clip_param_groups``, ``scaled_lr_groups``): with two or more groups every step form
+launches ``ops.adamw_step_groups``, one streaming launch per range with a per-slot group table.
+``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
 (configs/scheduler/cosine.yaml): the first optimiser step runs with lr = 0."""
 from __future__ import annotations
 
 import math
 import os
-from typing import Callable, Iterable, List, Optional, Tuple
+from typing import Any, Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -21,15 +24,26 @@ class FusedAdamW:
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2):
         params = list(params)
-        stores = {id(getattr(p, "_sc_store", None)): getattr(p, "_sc_store", None) for p in params}
-        if len(stores) != 1 or None in stores.values():
-            raise ValueError("FusedAdamW needs the parameters of exactly one SpatialClipNet (flat ParamStore)")
-        self.store = next(iter(stores.values()))
-        if len(params) != len(self.store.specs):
-            raise ValueError("FusedAdamW updates the whole flat buffer: pass all parameters (reference passes "
-                             "self.parameters() un-grouped)")
-        self.param_groups = [{"params": params, "lr": lr, "initial_lr": lr, "betas": tuple(betas), "eps": eps,
-                              "weight_decay": weight_decay}]
+        self.chunk_group: Optional[torch.Tensor] = None     # two or more groups: uint8 group of every 64-float slot (device)
+        self.group_hyper: Optional[torch.Tensor] = None     # ... and their device scalars (refresh_hyper / _refresh_group_hyper)
+        self._group_hyper_behind: Optional[torch.Tensor] = None     # the same for the form that launches on the communication stream
+        self._group_stage: list = []                         # pinned staging ring of the same: [host tensor, event of its copy]
+        self._group_stage_next = 0
+        if params and all(isinstance(g, Mapping) for g in params):
+            self._init_groups(params, lr, tuple(betas), eps, weight_decay)
+        else:
+            if any(isinstance(g, Mapping) for g in params):
+                raise ValueError("FusedAdamW: params mixes parameters and group dicts; pass either an iterable of parameters or "
+                                 "an iterable of {'params': [...], ...} dicts")
+            stores = {id(getattr(p, "_sc_store", None)): getattr(p, "_sc_store", None) for p in params}
+            if len(stores) != 1 or None in stores.values():
+                raise ValueError("FusedAdamW needs the parameters of exactly one SpatialClipNet (flat ParamStore)")
+            self.store = next(iter(stores.values()))
+            if len(params) != len(self.store.specs):
+                raise ValueError("FusedAdamW updates the whole flat buffer: pass all parameters (reference passes "
+                                 "self.parameters() un-grouped)")
+            self.param_groups = [{"params": params, "lr": lr, "initial_lr": lr, "betas": tuple(betas), "eps": eps,
+                                  "weight_decay": weight_decay}]
         # Locked towers (SpatialClipNet.lock_image_tower / lock_text_tower): Lightning still passes every parameter; the ones
         # with requires_grad=False get what torch.optim.AdamW gives a parameter without .grad -- no update, no weight decay, no
         # moments.  Every step form runs over the trainable ranges of the flat buffers (one range, the whole buffer, without a
@@ -53,6 +67,103 @@ class FusedAdamW:
         self.hyper = None           # fp32 [3] = {lr, 1 - beta1^step, sqrt(1 - beta2^step)}
         self._hyper_host = None     # pinned staging of the same
 
+    # ---- parameter groups
+    GROUP_KEYS = ("params", "lr", "weight_decay", "betas", "eps", "initial_lr", "param_names")
+    MAX_GROUPS = 256        # the slot table holds one byte per slot, the kernel 256 {decay, step} pairs in LDS
+
+    def _init_groups(self, groups: Sequence[Mapping], lr: float, betas, eps: float, weight_decay: float) -> None:
+        """``params`` as a list of group dicts: validate, lay ``param_groups`` out and -- with two or more groups -- build the
+        slot table.  Every failure is a ValueError that names the parameter or key."""
+        if len(groups) > self.MAX_GROUPS:
+            raise ValueError(f"FusedAdamW: {len(groups)} parameter groups; at most {self.MAX_GROUPS} are supported (one byte per "
+                             "64-float slot names the group)")
+        out, store, seen = [], None, {}
+        for gi, g in enumerate(groups):
+            unknown = [k for k in g if k not in self.GROUP_KEYS]
+            if unknown:
+                raise ValueError(f"FusedAdamW: parameter group {gi} has unknown key(s) {unknown}; accepted: "
+                                 f"{list(self.GROUP_KEYS)}")
+            if "params" not in g:
+                raise ValueError(f"FusedAdamW: parameter group {gi} has no 'params'")
+            if "betas" in g and tuple(float(b) for b in g["betas"]) != tuple(float(b) for b in betas):
+                raise ValueError(f"FusedAdamW: parameter group {gi} sets betas={tuple(g['betas'])}; per-group betas are not "
+                                 f"supported (the optimiser's are {tuple(betas)})")
+            if "eps" in g and float(g["eps"]) != float(eps):
+                raise ValueError(f"FusedAdamW: parameter group {gi} sets eps={g['eps']}; per-group eps is not supported (the "
+                                 f"optimiser's is {eps})")
+            ps = g["params"]
+            ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            names = []
+            for p in ps:
+                st = getattr(p, "_sc_store", None)
+                if st is None:
+                    raise ValueError(f"FusedAdamW: parameter group {gi} holds a tensor of shape {tuple(getattr(p, 'shape', ()))} "
+                                     "that is no parameter of a SpatialClipNet (flat ParamStore)")
+                if store is None:
+                    store = st
+                    by_id = {id(q): n for n, q in st.params.items()}
+                elif st is not store:
+                    raise ValueError(f"FusedAdamW: parameter group {gi} holds parameters of another SpatialClipNet; all groups "
+                                     "must share one flat ParamStore")
+                name = by_id[id(p)]
+                if name in seen:
+                    raise ValueError(f"FusedAdamW: parameter {name} is listed twice (groups {seen[name]} and {gi})")
+                seen[name] = gi
+                names.append(name)
+            g_lr = float(g.get("lr", lr))
+            out.append({"params": ps, "lr": g_lr, "initial_lr": float(g.get("initial_lr", g_lr)), "betas": tuple(betas),
+                        "eps": eps, "weight_decay": float(g.get("weight_decay", weight_decay)), "param_names": names})
+        if store is None:
+            raise ValueError("FusedAdamW: the parameter groups hold no parameters")
+        missing = [n for n, p in store.params.items() if p.requires_grad and n not in seen]
+        if missing:
+            raise ValueError(f"FusedAdamW: {len(missing)} trainable parameter(s) are in no group (first: {missing[0]}); every "
+                             "parameter with requires_grad=True must be in exactly one group")
+        self.store = store
+        self.param_groups = out
+        if len(out) > 1:
+            self.chunk_group = slot_table(store, [g["param_names"] for g in out]).to(store.device)
+            n = 2 + 2 * len(out)        # allocated here, on the stream the optimiser is built on, not inside a step
+            cuda = torch.device(store.device).type == "cuda"
+            self.group_hyper = torch.zeros(n, dtype=torch.float32, device=store.device)
+            self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=store.device)
+            for _ in range(4):
+                host = torch.zeros(n, dtype=torch.float32)
+                self._group_stage.append([host.pin_memory() if cuda else host, None])
+
+    def _refresh_group_hyper(self, behind: bool = False) -> torch.Tensor:
+        """Two or more groups: {1 - beta1^step, sqrt(1 - beta2^step)} and every group's {lr, weight_decay} for the step about
+        to run (``step_count`` already advanced) into device memory: one small async copy on the CURRENT stream, in front of
+        the launches that read it on that stream; returns the device table.  The forms that launch on the stream of the step
+        (one launch per range, graph-captured) share ``self.group_hyper``.  ``behind``: the form that launches on the
+        communication stream calls this with that stream current and has a table of its own, written and read on that stream
+        alone -- so the copy waits for nothing but the previous update and lands while the backward still runs, off the
+        path to the first bucket.  The pinned staging is a ring of four, each with the event of its last copy, so that a host
+        running ahead of the device never rewrites floats a pending copy still has to read."""
+        dev = self.store.device
+        cuda = torch.device(dev).type == "cuda"
+        slot = self._group_stage[self._group_stage_next]
+        self._group_stage_next = (self._group_stage_next + 1) % len(self._group_stage)
+        if slot[1] is not None:
+            slot[1].synchronize()
+        g0 = self.param_groups[0]
+        ops.adamw_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
+                                    g0["betas"][0], g0["betas"][1], self.step_count, slot[0])
+        table = self._group_hyper_behind if behind else self.group_hyper
+        table.copy_(slot[0], non_blocking=True)
+        if cuda:
+            slot[1] = torch.cuda.Event()
+            slot[1].record(torch.cuda.current_stream(dev))
+        return table
+
+    def _adamw_groups(self, k: int, lo: int, hi: int, grad_scale: float, clip, table: Optional[torch.Tensor] = None) -> None:
+        """The grouped update of flat[lo:hi], a piece of trainable range ``k`` (lo a multiple of 64): one launch."""
+        st, g = self.store, self.param_groups[0]
+        m, v = self._moments(k, lo, hi)
+        ops.adamw_step_groups(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.chunk_group[lo // 64:],
+                              self.group_hyper if table is None else table, len(self.param_groups), g["betas"][0],
+                              g["betas"][1], g["eps"], grad_scale, clip, st.master_bf16[lo:hi])
+
     def attach_exchange(self, exchange) -> None:
         """Data-parallel runs: hand the optimiser the gradient exchange of the process group.  With a
         ``comm.ShardedGradExchange`` the optimiser state shrinks to this rank's 1/W of every bucket (Adam moments: 8 bytes
@@ -63,6 +174,9 @@ class FusedAdamW:
         if not isinstance(exchange, comm.ShardedGradExchange):
             self.exchange = None
             return
+        if len(self.param_groups) > 1:
+            raise ValueError(f"FusedAdamW: {len(self.param_groups)} parameter groups with the sharded gradient exchange "
+                             "(SC_GRAD_EXCHANGE=sharded) are not supported; use the all-reduce exchange")
         if self.store.locked:
             raise ValueError("FusedAdamW: a locked tower with the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not "
                              "supported; use the all-reduce exchange")
@@ -164,16 +278,23 @@ class FusedAdamW:
         buckets, order, copies, plans, owner = self._behind_plan(int(os.environ.get("SC_ADAMW_BUCKET", 16 * 1024 * 1024)))
         cur = torch.cuda.current_stream(st.device)
         side = streams.comm_stream(st.device)       # (a low-priority stream of its own measured the same on ViT-B/16, worse on ViT-L/14)
+        table = None
+        if self.chunk_group is not None:
+            with torch.cuda.stream(side):   # in front of the wait for the backward: behind the last update in stream order only
+                table = self._refresh_group_hyper(behind=True)
         ready = torch.cuda.Event()
         ready.record(cur)
         side.wait_event(ready)
         with torch.cuda.stream(side):
             for k in order:
                 lo, hi = buckets[k]
-                m, v = self._moments(owner[k], lo, hi)
-                ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"],
-                               g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip,
-                               st.master_bf16[lo:hi])
+                if self.chunk_group is not None:
+                    self._adamw_groups(owner[k], lo, hi, grad_scale, clip, table)
+                else:
+                    m, v = self._moments(owner[k], lo, hi)
+                    ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"],
+                                   g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip,
+                                   st.master_bf16[lo:hi])
                 st.refresh_range(lo, hi, copies[k], plans[k], fresh=(lo, hi))
                 done = torch.cuda.Event()
                 done.record(side)
@@ -184,7 +305,10 @@ class FusedAdamW:
     def refresh_hyper(self) -> None:
         """Write {lr, 1 - beta1^step, sqrt(1 - beta2^step)} for the step about to run (``step_count`` already advanced) into
         the device triple ``self.hyper``: one 12-byte async H2D copy on the current stream, enqueued in front of the graph
-        replay that reads it."""
+        replay that reads it.  With two or more parameter groups: the group table ``self.group_hyper`` instead."""
+        if self.chunk_group is not None:
+            self._refresh_group_hyper()
+            return
         g = self.param_groups[0]
         if self.hyper is None:
             self.hyper = torch.zeros(3, dtype=torch.float32, device=self.store.device)
@@ -206,6 +330,9 @@ class FusedAdamW:
         st.wait_all()
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
         for k, (lo, hi) in enumerate(self.ranges):
+            if self.chunk_group is not None:
+                self._adamw_groups(k, lo, hi, grad_scale, clip)
+                continue
             m, v = self._moments(k, lo, hi)
             ops.adamw_step_dev(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.hyper, g["betas"][0],
                                g["betas"][1], g["eps"], g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
@@ -234,7 +361,12 @@ class FusedAdamW:
         if st.master.is_cuda and (behind == "1" or (behind not in ("0", "1") and st.total <= 200_000_000)):
             return self._step_behind_forward(grad_scale, max_norm, sumsq_partial)
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
+        if self.chunk_group is not None:
+            self._refresh_group_hyper()
         for k, (lo, hi) in enumerate(self.ranges):
+            if self.chunk_group is not None:
+                self._adamw_groups(k, lo, hi, grad_scale, clip)
+                continue
             m, v = self._moments(k, lo, hi)
             ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"], g["betas"][0],
                            g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16[lo:hi])
@@ -252,7 +384,7 @@ class FusedAdamW:
         else:       # the full flat layout, zeros in the locked ranges: the file resumes with or without the lock
             m, v = self._expand(self.exp_avg), self._expand(self.exp_avg_sq)
         return {"step": self.step_count, "exp_avg": m, "exp_avg_sq": v,
-                "param_groups": [{k: v_ for k, v_ in self.param_groups[0].items() if k != "params"}]}
+                "param_groups": [{k: v_ for k, v_ in g.items() if k != "params"} for g in self.param_groups]}
 
     def load_state_dict(self, sd) -> None:
         self.store.wait_all()
@@ -278,6 +410,141 @@ class FusedAdamW:
         for k, (lo, hi) in enumerate(self.ranges):
             full[lo:hi] = compact[self._moff[k]:self._moff[k] + hi - lo]
         return full
+
+
+def slot_table(store, group_names: Sequence[Sequence[str]]) -> torch.Tensor:
+    """uint8 [store.total // 64] on the host: the group of every 64-float slot of the flat buffers.  A parameter starts on a
+    slot boundary and shares no slot with another (params.ALIGN), so each of its slots -- the zero padding of its last one
+    included -- carries its group; slots of no listed parameter (the padding behind the last parameter, locked parameters
+    left out of every group) read 0: their gradients are zero or no launch covers them."""
+    from .params import ALIGN
+    if ALIGN != 64:
+        raise ValueError(f"slot_table: the grouped AdamW kernel maps float4 i to slot i >> 4; params.ALIGN is {ALIGN}, not 64")
+    if len(group_names) > FusedAdamW.MAX_GROUPS:
+        raise ValueError(f"slot_table: {len(group_names)} groups; at most {FusedAdamW.MAX_GROUPS}")
+    table = torch.zeros(store.total // ALIGN, dtype=torch.uint8)
+    for gi, names in enumerate(group_names):
+        for name in names:
+            sp = store.by_name[name]
+            lo = sp.offset // ALIGN
+            table[lo:lo + (max(sp.numel, 1) + ALIGN - 1) // ALIGN] = gi
+    return table
+
+
+def _reference_name(name: str, p) -> str:
+    """The state-dict name of ``p``: the ParamStore's, if ``p`` is one of a store's parameters (``net.named_parameters()``
+    spells ``visual.proj`` as ``visual__proj``); otherwise the name given."""
+    st = getattr(p, "_sc_store", None)
+    if st is not None:
+        for n, q in st.params.items():
+            if q is p:
+                return n
+    return name
+
+
+NO_DECAY_MARKERS = ("bn", "ln", "bias", "logit_scale")
+
+
+def open_clip_param_groups(named_parameters, weight_decay: Optional[float] = None) -> List[Dict[str, Any]]:
+    """The two groups open_clip trains with: gains, biases and scalars -- every tensor with fewer than two dimensions, and every
+    tensor whose state-dict name contains ``bn``, ``ln``, ``bias`` or ``logit_scale`` -- get ``weight_decay = 0`` (first group);
+    everything else gets ``weight_decay`` (second group; ``None`` leaves it to the optimiser's default).  ``named_parameters``:
+    ``(name, tensor)`` pairs, e.g. ``net.named_parameters()``; names are looked up in the ParamStore.  An ``nn.Parameter`` with
+    ``requires_grad=False`` (a locked tower) is left out, as open_clip leaves it out.  An empty group is dropped."""
+    no_decay: Dict[str, list] = {"params": [], "weight_decay": 0.0, "param_names": []}
+    decay: Dict[str, Any] = {"params": [], "param_names": []}
+    if weight_decay is not None:
+        decay["weight_decay"] = float(weight_decay)
+    for name, p in named_parameters:
+        if isinstance(p, torch.nn.Parameter) and not p.requires_grad:
+            continue
+        name = _reference_name(name, p)
+        g = no_decay if p.ndim < 2 or any(mark in name for mark in NO_DECAY_MARKERS) else decay
+        g["params"].append(p)
+        g["param_names"].append(name)
+    return [g for g in (no_decay, decay) if g["params"]]
+
+
+def scaled_lr_groups(groups: Sequence[Mapping], lr: float, lr_scale: Mapping[str, float]) -> List[Dict[str, Any]]:
+    """Split every group by the longest prefix in ``lr_scale`` that its parameters' state-dict names start with: the
+    parameters under prefix ``q`` move to a group of their own with ``lr = base * lr_scale[q]`` (``base``: the group's own
+    ``lr``, else ``lr``); the others stay as they were.  ``{"visual.": 0.1}`` trains the image tower at a tenth of ``lr``.
+    The order of the groups and of the parameters inside them is kept; empty groups are dropped."""
+    scales = check_lr_scale(lr_scale)
+    prefixes = sorted(scales, key=len, reverse=True)
+    out: List[Dict[str, Any]] = []
+    for g in groups:
+        ps = g["params"]
+        ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+        given = list(g.get("param_names", ()))
+        if given and len(given) != len(ps):
+            raise ValueError(f"scaled_lr_groups: a group lists {len(ps)} parameters and {len(given)} param_names")
+        names = [_reference_name(given[i] if given else "", p) for i, p in enumerate(ps)]
+        parts: Dict[Optional[str], Tuple[list, list]] = {}
+        for name, p in zip(names, ps):
+            key = next((q for q in prefixes if name.startswith(q)), None)
+            part = parts.setdefault(key, ([], []))
+            part[0].append(p)
+            part[1].append(name)
+        for key in [None] + [q for q in scales if q in parts]:
+            if key not in parts:
+                continue
+            new = {k: v for k, v in g.items() if k not in ("params", "param_names", "initial_lr")}
+            new["params"], new["param_names"] = parts[key]
+            if key is not None:
+                new["lr"] = float(g.get("lr", lr)) * scales[key]
+            out.append(new)
+    return out
+
+
+def check_lr_scale(lr_scale) -> Dict[str, float]:
+    """``{name prefix: positive factor}`` or ValueError naming the offending entry."""
+    if not isinstance(lr_scale, Mapping):
+        raise ValueError(f"lr_scale={lr_scale!r}: a mapping {{name prefix: factor}} is expected")
+    out = {}
+    for prefix, factor in lr_scale.items():
+        ok = isinstance(factor, (int, float)) and not isinstance(factor, bool) and math.isfinite(factor) and factor > 0
+        if not isinstance(prefix, str) or not prefix or not ok:
+            raise ValueError(f"lr_scale[{prefix!r}]={factor!r}: a non-empty name prefix and a positive, finite factor are "
+                             "expected")
+        out[prefix] = float(factor)
+    return out
+
+
+PARAM_GROUPS_KEYS = ("no_decay", "lr_scale")
+
+
+def check_param_groups_cfg(cfg):
+    """``SpatialClipLitModule(param_groups=...)`` / the config key ``model.param_groups``: None, a callable ``(net) -> list of
+    group dicts``, or a mapping ``{"no_decay": "open_clip" | None, "lr_scale": {prefix: factor}}``.  Returns it (a mapping as a
+    plain dict); ValueError names an unknown key, another ``no_decay`` rule or a bad scale."""
+    if cfg is None or callable(cfg):
+        return cfg
+    if not isinstance(cfg, Mapping):
+        raise ValueError(f"param_groups={cfg!r}: None, a callable (net) -> groups, or a mapping with the keys "
+                         f"{list(PARAM_GROUPS_KEYS)} is expected")
+    unknown = [k for k in cfg if k not in PARAM_GROUPS_KEYS]
+    if unknown:
+        raise ValueError(f"param_groups: unknown key(s) {unknown}; accepted: {list(PARAM_GROUPS_KEYS)}")
+    no_decay = cfg.get("no_decay")
+    if no_decay not in (None, "open_clip"):
+        raise ValueError(f"param_groups.no_decay={no_decay!r}: 'open_clip' (gains, biases and scalars without weight decay) or "
+                         "null")
+    scales = cfg.get("lr_scale")
+    return {"no_decay": no_decay, "lr_scale": check_lr_scale(scales) if scales is not None else None}
+
+
+def build_param_groups(net, cfg, lr: float, weight_decay: Optional[float] = None) -> List[Dict[str, Any]]:
+    """The group dicts of ``check_param_groups_cfg``'s mapping for ``net``, over its trainable parameters."""
+    store = net.store
+    named = [(n, p) for n, p in store.params.items() if p.requires_grad]
+    if cfg.get("no_decay") == "open_clip":
+        groups = open_clip_param_groups(named, weight_decay)
+    else:
+        groups = [{"params": [p for _, p in named], "param_names": [n for n, _ in named]}]
+    if cfg.get("lr_scale"):
+        groups = scaled_lr_groups(groups, lr, cfg["lr_scale"])
+    return groups
 
 
 class GradAccumulator:
