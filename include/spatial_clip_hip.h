@@ -502,6 +502,28 @@ int sc_adamw_groups_hyper_host(const float* lr, const float* wd, int n_groups, f
 int sc_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                          const unsigned char* chunk_group, const float* group_hyper, int n_groups, float beta1, float beta2,
                          float eps, float grad_scale, const float* norm_clip, void* params_bf16, void* stream);
+/* Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms", Algorithm 1 -- open_clip's `--opt timm/lion`,
+ * src/open_clip_train/main.py:319-337) over the same flat buffers, with ONE moment.  For ge = g * grad_scale * clip
+ * (clip = norm_clip[1], or 1 when norm_clip is NULL):
+ *   c = beta1 * m + (1 - beta1) * ge;   p = p * (1 - lr * wd) - lr * sign(c);   m = beta2 * m + (1 - beta2) * ge
+ * Decoupled weight decay first, no bias correction, no eps; sign(0) = 0 (also for -0.0), so the zero padding of the flat
+ * buffers stays zero.  22 bytes per parameter (12 read, 10 written with the bf16 mirror) against AdamW's 30.  The three
+ * forms mirror the AdamW ones and share one kernel body: sc_lion_step_dev reads lr from ONE device float (a captured
+ * hipGraph replays an identical launch) and gives the bits of sc_lion_step; sc_lion_step_groups takes the slot table of
+ * sc_adamw_step_groups and group_hyper (DEVICE, 2 * n_groups floats) = {lr_g, wd_g} per group, as
+ * sc_lion_groups_hyper_host lays them out in a HOST buffer, and gives every slot of group g the bits of sc_lion_step run on
+ * it with (lr_g, wd_g).  n: a positive multiple of 4 (of 64 for the grouped form); 1 <= n_groups <= 256; params, grads,
+ * exp_avg (and lr_dev / chunk_group / group_hyper) must not be NULL; norm_clip and params_bf16 may be.  A refusal sets
+ * sc_last_error and launches nothing. */
+int sc_lion_step(float* params, const float* grads, float* exp_avg, long long n, float lr, float beta1, float beta2,
+                 float weight_decay, float grad_scale, const float* norm_clip, void* params_bf16, void* stream);
+int sc_lion_step_dev(float* params, const float* grads, float* exp_avg, long long n, const float* lr_dev, float beta1,
+                     float beta2, float weight_decay, float grad_scale, const float* norm_clip, void* params_bf16,
+                     void* stream);
+int sc_lion_groups_hyper_host(const float* lr, const float* wd, int n_groups, float* out_host);
+int sc_lion_step_groups(float* params, const float* grads, float* exp_avg, long long n, const unsigned char* chunk_group,
+                        const float* group_hyper, int n_groups, float beta1, float beta2, float grad_scale,
+                        const float* norm_clip, void* params_bf16, void* stream);
 /* The two halves of sc_grad_norm for an optimiser that owns 1/W of every gradient bucket (reduce-scatter ->
  * AdamW on the rank's shard -> all-gather; Lightning's DDP mean, configs/trainer/ddp.yaml:4, replaced): 1024 fp64 partial
  * sums of squares per contiguous piece of the shard, then -- after the caller has all-reduced (SUM) the concatenated

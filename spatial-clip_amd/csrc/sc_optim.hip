@@ -143,6 +143,71 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     }
 }
 
+// ---- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms", Algorithm 1; lion_pytorch.Lion, timm.optim.Lion):
+// one moment, the update is the SIGN of an interpolation between moment and gradient:
+//   c = b1 * m + (1 - b1) * ge;   p = p * (1 - lr * wd) - lr * sign(c);   m = b2 * m + (1 - b2) * ge
+// with ge = g * grad_scale * clip as in adamw_kernel, decoupled weight decay applied first, no bias correction, no eps.
+// sign(0) = 0: the zero padding of every parameter's last slot (p = g = m = 0) has c = 0 and must stay at zero.
+// 22 bytes per parameter: 12 read (p, g, m), 10 written (p, m, bf16 mirror) against adamw_kernel's 30.
+// ONE body for the three launch forms (host scalars, lr from device memory, per-slot groups): under -ffp-contract=fast the
+// same source shape gets the same contractions, so the forms agree bit for bit (see adamw_groups_kernel above).
+SC_DEVICE void lion_update(f32x4& pp, const f32x4& gg, f32x4& mm, float decay, float lr, float b1, float b2, float gs) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float ge = gg[c] * gs;
+        const float cc = b1 * mm[c] + (1.0f - b1) * ge;
+        const float upd = cc > 0.0f ? lr : (cc < 0.0f ? -lr : 0.0f);      // lr * sign(cc); 0 for cc = +-0 (and NaN)
+        pp[c] *= decay;
+        pp[c] -= upd;
+        mm[c] = b2 * mm[c] + (1.0f - b2) * ge;
+    }
+}
+
+// GROUPS = false: lr / wd are the arguments, or lr = lr_dev[0] when lr_dev is given (a captured hipGraph replays the launch).
+// GROUPS = true: hyper (DEVICE) = {lr_g, wd_g} per group, chunk_group names the group of each 64-float slot (float4 i belongs
+// to slot i >> 4); {decay, lr} of every group are formed at block start with the expression of the un-grouped form.
+template <bool GROUPS>
+__global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   long long n, float lr, float wd, float b1, float b2, float gscale,
+                                                   const float* __restrict__ normclip, bf16* __restrict__ pbf,
+                                                   const float* __restrict__ lr_dev,
+                                                   const unsigned char* __restrict__ chunk_group,
+                                                   const float* __restrict__ hyper, int n_groups) {
+    __shared__ float2 group_scalars[GROUPS ? 256 : 1];      // {decay, lr} of each group
+    float decay = 0.f;
+    if (GROUPS) {
+        if ((int)threadIdx.x < n_groups) {
+            const float lr_g = hyper[2 * threadIdx.x], wd_g = hyper[2 * threadIdx.x + 1];
+            group_scalars[threadIdx.x] = make_float2(1.0f - lr_g * wd_g, lr_g);
+        }
+        __syncthreads();
+    } else {
+        if (lr_dev != nullptr) lr = lr_dev[0];
+        decay = 1.0f - lr * wd;
+    }
+    const float gs = gscale * (normclip ? normclip[1] : 1.0f);
+    const long long n4 = n >> 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (long long)gridDim.x * blockDim.x) {
+        if (GROUPS) {
+            const float2 ds = group_scalars[chunk_group[i >> 4]];
+            decay = ds.x;
+            lr = ds.y;
+        }
+        f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
+        lion_update(pp, gg, mm, decay, lr, b1, b2, gs);
+        reinterpret_cast<f32x4*>(p)[i] = pp;
+        if (pbf) {      // bf16 mirror of the master buffer, as adamw_kernel writes it
+            bf16x4 o;
+            o[0] = (bf16)pp[0]; o[1] = (bf16)pp[1]; o[2] = (bf16)pp[2]; o[3] = (bf16)pp[3];
+            reinterpret_cast<bf16x4*>(pbf)[i] = o;
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mm;
+    }
+}
+
 // ---- gradient accumulation (Trainer accumulate_grad_batches): every backward OVERWRITES the flat gradient buffer, so the
 // sum over the micro-batches of a group is a running fp32 buffer beside it, folded once per micro-batch by this kernel:
 //   mode 0 (first)  acc   = scale * grads
@@ -372,6 +437,65 @@ extern "C" int sc_adamw_step_groups(float* params, const float* grads, float* ex
     adamw_groups_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, chunk_group, group_hyper,
                                                                   n_groups, beta1, beta2, eps, grad_scale, norm_clip,
                                                                   (bf16*)params_bf16);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- Lion: the three launch forms of lion_kernel, in the shape of the AdamW entry points (one moment, no eps, no step
+// number: there is no bias correction).  n: a positive multiple of 4 (64 for the grouped form); params, grads and exp_avg are
+// required, norm_clip and params_bf16 may be NULL.  A refusal launches nothing.
+static inline int lion_blocks(long long n) {
+    long long nb = (n / 4 + 255) / 256;
+    return (int)(nb > 4096 ? 4096 : nb);
+}
+
+extern "C" int sc_lion_step(float* params, const float* grads, float* exp_avg, long long n, float lr, float beta1, float beta2,
+                            float weight_decay, float grad_scale, const float* norm_clip, void* params_bf16, void* stream) {
+    SC_CHECK(n > 0 && (n % 4) == 0, "sc_lion_step: n = %lld must be a positive multiple of 4", n);
+    SC_CHECK(params && grads && exp_avg, "sc_lion_step: params, grads and exp_avg are required");
+    lion_kernel<false><<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, n, lr, weight_decay, beta1, beta2,
+                                                                       grad_scale, norm_clip, (bf16*)params_bf16, nullptr,
+                                                                       nullptr, nullptr, 0);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// lr from ONE device float: the launch is identical from step to step (graph.GraphedTrainStep); same bits as sc_lion_step.
+extern "C" int sc_lion_step_dev(float* params, const float* grads, float* exp_avg, long long n, const float* lr_dev, float beta1,
+                                float beta2, float weight_decay, float grad_scale, const float* norm_clip, void* params_bf16,
+                                void* stream) {
+    SC_CHECK(n > 0 && (n % 4) == 0, "sc_lion_step_dev: n = %lld must be a positive multiple of 4", n);
+    SC_CHECK(params && grads && exp_avg, "sc_lion_step_dev: params, grads and exp_avg are required");
+    SC_CHECK(lr_dev != nullptr, "sc_lion_step_dev: lr_dev is required");
+    lion_kernel<false><<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, n, 0.f, weight_decay, beta1, beta2,
+                                                                       grad_scale, norm_clip, (bf16*)params_bf16, lr_dev,
+                                                                       nullptr, nullptr, 0);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// Parameter groups: host-side {lr_g, wd_g} per group (2 * n_groups floats) for the small pinned -> device copy in front of
+// sc_lion_step_groups.
+extern "C" int sc_lion_groups_hyper_host(const float* lr, const float* wd, int n_groups, float* out_host) {
+    SC_CHECK(lr != nullptr && wd != nullptr && out_host != nullptr, "sc_lion_groups_hyper_host: lr, wd and the host output are required");
+    SC_CHECK(n_groups >= 1 && n_groups <= 256, "sc_lion_groups_hyper_host: n_groups = %d (1 .. 256)", n_groups);
+    for (int k = 0; k < n_groups; ++k) {
+        out_host[2 * k] = lr[k];
+        out_host[2 * k + 1] = wd[k];
+    }
+    return 0;
+}
+
+extern "C" int sc_lion_step_groups(float* params, const float* grads, float* exp_avg, long long n,
+                                   const unsigned char* chunk_group, const float* group_hyper, int n_groups, float beta1,
+                                   float beta2, float grad_scale, const float* norm_clip, void* params_bf16, void* stream) {
+    SC_CHECK(n > 0 && (n % 64) == 0, "sc_lion_step_groups: n = %lld must be a positive multiple of 64 (whole slots)", n);
+    SC_CHECK(n_groups >= 1 && n_groups <= 256, "sc_lion_step_groups: n_groups = %d (1 .. 256)", n_groups);
+    SC_CHECK(chunk_group != nullptr && group_hyper != nullptr, "sc_lion_step_groups: chunk_group and group_hyper are required");
+    SC_CHECK(params && grads && exp_avg, "sc_lion_step_groups: params, grads and exp_avg are required");
+    lion_kernel<true><<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, n, 0.f, 0.f, beta1, beta2, grad_scale,
+                                                                      norm_clip, (bf16*)params_bf16, nullptr, chunk_group,
+                                                                      group_hyper, n_groups);
     SC_LAUNCH_CHECK();
     return 0;
 }

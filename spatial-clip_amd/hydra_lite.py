@@ -34,6 +34,9 @@ TARGET_MAP = {
     "src.data.spatial_datamodule.SpatialClipDataModule": "spatial_clip_amd.data.SpatialClipDataModule",
     "open_clip.AugmentationCfg": "spatial_clip_amd.net.AugmentationCfg",
     "torch.optim.AdamW": "spatial_clip_amd.optim.FusedAdamW",
+    "lion_pytorch.Lion": "spatial_clip_amd.optim.FusedLion",
+    "timm.optim.Lion": "spatial_clip_amd.optim.FusedLion",
+    "timm.optim.lion.Lion": "spatial_clip_amd.optim.FusedLion",
     "transformers.get_cosine_schedule_with_warmup": "spatial_clip_amd.optim.get_cosine_schedule_with_warmup",
     "lightning.pytorch.Trainer": "spatial_clip_amd.trainer.Trainer",
     "lightning.Trainer": "spatial_clip_amd.trainer.Trainer",

@@ -854,6 +854,72 @@ def adamw_step_groups(p, g, m, v, n, chunk_group, group_hyper, n_groups, beta1, 
                                           _ptr(norm_clip), _ptr(p_bf16), _stream()), "sc_adamw_step_groups")
 
 
+def _lion_buffers(what, p, g, m, n, p_bf16):
+    for t, name in ((p, "p"), (g, "g"), (m, "m")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"{what}: {name} holds {t.numel()} floats, n = {n}")
+    if p_bf16 is not None and p_bf16.numel() < n:
+        raise ValueError(f"{what}: the bf16 mirror holds {p_bf16.numel()} elements, n = {n}")
+
+
+def lion_step(p, g, m, n, lr, beta1, beta2, wd, grad_scale, norm_clip, p_bf16=None):
+    """Lion over flat[:n] (``sc_lion_step``): ``c = b1 m + (1 - b1) ge; p = p (1 - lr wd) - lr sign(c); m = b2 m + (1 - b2) ge``
+    with ``ge = g * grad_scale * norm_clip[1]``; one moment, ``sign(0) = 0``; the bf16 mirror is written when given."""
+    n = int(n)
+    _lion_buffers("lion_step", p, g, m, n, p_bf16)
+    check(_lib.lib().sc_lion_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), n, float(lr), float(beta1), float(beta2), float(wd),
+                                  float(grad_scale), _ptr(norm_clip), _ptr(p_bf16), _stream()), "sc_lion_step")
+
+
+def lion_step_dev(p, g, m, n, lr_dev, beta1, beta2, wd, grad_scale, norm_clip, p_bf16=None):
+    """``lion_step`` with the learning rate read from the one-float device tensor ``lr_dev`` (graph-captured steps); ``None``
+    is passed on as NULL, which the library refuses."""
+    n = int(n)
+    if lr_dev is not None:
+        _req(lr_dev, torch.float32, "lr_dev")
+        if lr_dev.numel() < 1:
+            raise ValueError("lion_step_dev: lr_dev holds no float")
+    _lion_buffers("lion_step_dev", p, g, m, n, p_bf16)
+    check(_lib.lib().sc_lion_step_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), n, _ptr(lr_dev), float(beta1), float(beta2),
+                                      float(wd), float(grad_scale), _ptr(norm_clip), _ptr(p_bf16), _stream()),
+          "sc_lion_step_dev")
+
+
+def lion_groups_hyper_host(lr, wd, out_host):
+    """Fill the HOST fp32 tensor ``out_host`` (2 * len(lr) floats, pinned for an async copy) with {lr_g, wd_g} per group: what
+    ``lion_step_groups`` reads from its device copy."""
+    n_groups = len(lr)
+    if len(wd) != n_groups:
+        raise ValueError(f"lion_groups_hyper_host: {n_groups} learning rates, {len(wd)} weight decays")
+    if out_host.is_cuda or out_host.dtype != torch.float32 or not out_host.is_contiguous() or out_host.numel() < 2 * n_groups:
+        raise ValueError(f"lion_groups_hyper_host: out_host must be {2 * n_groups} contiguous float32 in host memory")
+    arr = ctypes.c_float * max(n_groups, 1)
+    check(_lib.lib().sc_lion_groups_hyper_host(arr(*[float(x) for x in lr]), arr(*[float(x) for x in wd]), n_groups,
+                                               out_host.data_ptr()), "sc_lion_groups_hyper_host")
+    return out_host
+
+
+def lion_step_groups(p, g, m, n, chunk_group, group_hyper, n_groups, beta1, beta2, grad_scale, norm_clip, p_bf16=None):
+    """Lion over one range of the flat buffers with per-group lr / weight decay, one launch: ``chunk_group`` (uint8, device)
+    names the group of each 64-float slot of the range, ``group_hyper`` (fp32, device) is ``lion_groups_hyper_host``'s layout.
+    ``None`` for either is passed on as NULL, which the library refuses."""
+    n, n_groups = int(n), int(n_groups)
+    if chunk_group is not None:
+        _req(chunk_group, torch.uint8, "chunk_group")
+        if n > 0 and chunk_group.numel() < n // 64:
+            raise ValueError(f"lion_step_groups: chunk_group holds {chunk_group.numel()} slots, the range has {n // 64}")
+    if group_hyper is not None:
+        _req(group_hyper, torch.float32, "group_hyper")
+        if 1 <= n_groups <= 256 and group_hyper.numel() < 2 * n_groups:
+            raise ValueError(f"lion_step_groups: group_hyper holds {group_hyper.numel()} floats, {n_groups} groups need "
+                             f"{2 * n_groups}")
+    _lion_buffers("lion_step_groups", p, g, m, n, p_bf16)
+    check(_lib.lib().sc_lion_step_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), n, _ptr(chunk_group), _ptr(group_hyper),
+                                         n_groups, float(beta1), float(beta2), float(grad_scale), _ptr(norm_clip), _ptr(p_bf16),
+                                         _stream()), "sc_lion_step_groups")
+
+
 def cast_transpose_batched(master, desc, tile_prefix, n, total_tiles, mirror_bf16=None):
     check(_lib.lib().sc_cast_transpose_batched(master.data_ptr(), _ptr(mirror_bf16), desc.data_ptr(),
                                                tile_prefix.data_ptr(), n, total_tiles, _stream()),

@@ -7,6 +7,8 @@ parameters (the reference passes ``self.parameters()`` un-grouped, src/models/sp
 bf16 compute-copy refresh.  ``params`` may also be torch's other form, a list of ``{"params": [...], "lr": ...,
 "weight_decay": ...}`` dicts (``open_clip_param_groups``, ``scaled_lr_groups``): with two or more groups every step form
 launches ``ops.adamw_step_groups``, one streaming launch per range with a per-slot group table.
+``FusedLion(params, lr, betas, weight_decay)`` takes the kwargs of ``lion_pytorch.Lion`` / ``timm.optim.Lion`` and runs the
+same step forms with one moment (``ops.lion_step*``); both are ``_FlatOptimizer`` with their own launches.
 ``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
 (configs/scheduler/cosine.yaml): the first optimiser step runs with lr = 0."""
 from __future__ import annotations
@@ -20,9 +22,19 @@ import torch
 from . import ops
 
 
-class FusedAdamW:
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2):
+class _FlatOptimizer:
+    """Everything the fused optimisers share: parameter groups and their slot table, trainable ranges and the compact moment
+    layout under a lock, the clip, every step form (one launch per range, bucket by bucket behind the next forward, the
+    graph-captured form, the sharded form) and the checkpoint layout.  A subclass names itself (``NAME``), lists its state
+    tensors (``STATE``: attributes of that name, one flat fp32 buffer each) and supplies the launches: ``_update`` (a piece
+    with host scalars), ``_update_dev`` (the same with its step-dependent scalars in device memory), ``_update_groups`` (the
+    grouped form), ``_refresh_scalar_hyper`` / ``_fill_group_hyper`` (the device scalars of the step about to run)."""
+    NAME = ""
+    STATE: Tuple[str, ...] = ()
+    KIND: Optional[str] = None      # the "optimizer" entry of state_dict(); None: the key is not written (AdamW files)
+    SHARDABLE = True                # comm.ShardedGradExchange is supported
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, betas, eps: Optional[float], weight_decay: float):
         params = list(params)
         self.chunk_group: Optional[torch.Tensor] = None     # two or more groups: uint8 group of every 64-float slot (device)
         self.group_hyper: Optional[torch.Tensor] = None     # ... and their device scalars (refresh_hyper / _refresh_group_hyper)
@@ -33,17 +45,17 @@ class FusedAdamW:
             self._init_groups(params, lr, tuple(betas), eps, weight_decay)
         else:
             if any(isinstance(g, Mapping) for g in params):
-                raise ValueError("FusedAdamW: params mixes parameters and group dicts; pass either an iterable of parameters or "
+                raise ValueError(f"{self.NAME}: params mixes parameters and group dicts; pass either an iterable of parameters or "
                                  "an iterable of {'params': [...], ...} dicts")
             stores = {id(getattr(p, "_sc_store", None)): getattr(p, "_sc_store", None) for p in params}
             if len(stores) != 1 or None in stores.values():
-                raise ValueError("FusedAdamW needs the parameters of exactly one SpatialClipNet (flat ParamStore)")
+                raise ValueError(f"{self.NAME} needs the parameters of exactly one SpatialClipNet (flat ParamStore)")
             self.store = next(iter(stores.values()))
             if len(params) != len(self.store.specs):
-                raise ValueError("FusedAdamW updates the whole flat buffer: pass all parameters (reference passes "
+                raise ValueError(f"{self.NAME} updates the whole flat buffer: pass all parameters (reference passes "
                                  "self.parameters() un-grouped)")
-            self.param_groups = [{"params": params, "lr": lr, "initial_lr": lr, "betas": tuple(betas), "eps": eps,
-                                  "weight_decay": weight_decay}]
+            self.param_groups = [{"params": params, "lr": lr, "initial_lr": lr, "betas": tuple(betas),
+                                  **({} if eps is None else {"eps": eps}), "weight_decay": weight_decay}]
         # Locked towers (SpatialClipNet.lock_image_tower / lock_text_tower): Lightning still passes every parameter; the ones
         # with requires_grad=False get what torch.optim.AdamW gives a parameter without .grad -- no update, no weight decay, no
         # moments.  Every step form runs over the trainable ranges of the flat buffers (one range, the whole buffer, without a
@@ -56,16 +68,46 @@ class FusedAdamW:
             n += hi - lo
         self.store.optimizer_built = True       # the lock methods refuse from here on
         dev = self.store.device
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._alloc_state(n)
         self.norm_clip = torch.zeros(2, dtype=torch.float32, device=dev)
         self._range_partials: Optional[torch.Tensor] = None     # locked: 1024 fp64 sums of squares per trainable range
         self.step_count = 0
         self.exchange = None        # comm.ShardedGradExchange when this rank owns 1/W of every gradient bucket
         self._behind = None         # bucket plan of the replicated optimiser's overlapped form (_step_behind_forward)
         # graph-captured steps (graph.GraphedTrainStep): the step-dependent scalars live in device memory
-        self.hyper = None           # fp32 [3] = {lr, 1 - beta1^step, sqrt(1 - beta2^step)}
+        self.hyper = None           # fp32, what _refresh_scalar_hyper writes (AdamW: {lr, 1 - beta1^step, sqrt(1 - beta2^step)})
         self._hyper_host = None     # pinned staging of the same
+
+    def _alloc_state(self, n: int) -> None:
+        for name in self.STATE:
+            setattr(self, name, torch.zeros(n, dtype=torch.float32, device=self.store.device))
+
+    def _state(self) -> List[torch.Tensor]:
+        return [getattr(self, name) for name in self.STATE]
+
+    # ---- the launches a subclass supplies
+    def _update(self, lo: int, hi: int, moments, grad_scale: float, clip) -> None:
+        """flat[lo:hi] with the scalars of ``param_groups[0]`` as host arguments; ``moments``: the state slices of the piece."""
+        raise NotImplementedError
+
+    def _update_dev(self, lo: int, hi: int, moments, grad_scale: float, clip) -> None:
+        """The same with the step-dependent scalars read from ``self.hyper`` (``_refresh_scalar_hyper``)."""
+        raise NotImplementedError
+
+    def _update_groups(self, lo: int, hi: int, moments, grad_scale: float, clip, table: torch.Tensor) -> None:
+        """The grouped form: one launch, slot table ``self.chunk_group[lo // 64:]``, device scalars ``table``."""
+        raise NotImplementedError
+
+    def _refresh_scalar_hyper(self) -> None:
+        """One group: the step-dependent scalars of the step about to run into ``self.hyper`` (an async copy)."""
+        raise NotImplementedError
+
+    def _group_hyper_floats(self, n_groups: int) -> int:
+        raise NotImplementedError
+
+    def _fill_group_hyper(self, host: torch.Tensor) -> None:
+        """Two or more groups: the same for every group into the pinned HOST tensor ``host``."""
+        raise NotImplementedError
 
     # ---- parameter groups
     GROUP_KEYS = ("params", "lr", "weight_decay", "betas", "eps", "initial_lr", "param_names")
@@ -75,21 +117,21 @@ class FusedAdamW:
         """``params`` as a list of group dicts: validate, lay ``param_groups`` out and -- with two or more groups -- build the
         slot table.  Every failure is a ValueError that names the parameter or key."""
         if len(groups) > self.MAX_GROUPS:
-            raise ValueError(f"FusedAdamW: {len(groups)} parameter groups; at most {self.MAX_GROUPS} are supported (one byte per "
+            raise ValueError(f"{self.NAME}: {len(groups)} parameter groups; at most {self.MAX_GROUPS} are supported (one byte per "
                              "64-float slot names the group)")
         out, store, seen = [], None, {}
         for gi, g in enumerate(groups):
             unknown = [k for k in g if k not in self.GROUP_KEYS]
             if unknown:
-                raise ValueError(f"FusedAdamW: parameter group {gi} has unknown key(s) {unknown}; accepted: "
+                raise ValueError(f"{self.NAME}: parameter group {gi} has unknown key(s) {unknown}; accepted: "
                                  f"{list(self.GROUP_KEYS)}")
             if "params" not in g:
-                raise ValueError(f"FusedAdamW: parameter group {gi} has no 'params'")
+                raise ValueError(f"{self.NAME}: parameter group {gi} has no 'params'")
             if "betas" in g and tuple(float(b) for b in g["betas"]) != tuple(float(b) for b in betas):
-                raise ValueError(f"FusedAdamW: parameter group {gi} sets betas={tuple(g['betas'])}; per-group betas are not "
+                raise ValueError(f"{self.NAME}: parameter group {gi} sets betas={tuple(g['betas'])}; per-group betas are not "
                                  f"supported (the optimiser's are {tuple(betas)})")
             if "eps" in g and float(g["eps"]) != float(eps):
-                raise ValueError(f"FusedAdamW: parameter group {gi} sets eps={g['eps']}; per-group eps is not supported (the "
+                raise ValueError(f"{self.NAME}: parameter group {gi} sets eps={g['eps']}; per-group eps is not supported (the "
                                  f"optimiser's is {eps})")
             ps = g["params"]
             ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
@@ -97,33 +139,34 @@ class FusedAdamW:
             for p in ps:
                 st = getattr(p, "_sc_store", None)
                 if st is None:
-                    raise ValueError(f"FusedAdamW: parameter group {gi} holds a tensor of shape {tuple(getattr(p, 'shape', ()))} "
+                    raise ValueError(f"{self.NAME}: parameter group {gi} holds a tensor of shape {tuple(getattr(p, 'shape', ()))} "
                                      "that is no parameter of a SpatialClipNet (flat ParamStore)")
                 if store is None:
                     store = st
                     by_id = {id(q): n for n, q in st.params.items()}
                 elif st is not store:
-                    raise ValueError(f"FusedAdamW: parameter group {gi} holds parameters of another SpatialClipNet; all groups "
+                    raise ValueError(f"{self.NAME}: parameter group {gi} holds parameters of another SpatialClipNet; all groups "
                                      "must share one flat ParamStore")
                 name = by_id[id(p)]
                 if name in seen:
-                    raise ValueError(f"FusedAdamW: parameter {name} is listed twice (groups {seen[name]} and {gi})")
+                    raise ValueError(f"{self.NAME}: parameter {name} is listed twice (groups {seen[name]} and {gi})")
                 seen[name] = gi
                 names.append(name)
             g_lr = float(g.get("lr", lr))
             out.append({"params": ps, "lr": g_lr, "initial_lr": float(g.get("initial_lr", g_lr)), "betas": tuple(betas),
-                        "eps": eps, "weight_decay": float(g.get("weight_decay", weight_decay)), "param_names": names})
+                        **({} if eps is None else {"eps": eps}), "weight_decay": float(g.get("weight_decay", weight_decay)),
+                        "param_names": names})
         if store is None:
-            raise ValueError("FusedAdamW: the parameter groups hold no parameters")
+            raise ValueError(f"{self.NAME}: the parameter groups hold no parameters")
         missing = [n for n, p in store.params.items() if p.requires_grad and n not in seen]
         if missing:
-            raise ValueError(f"FusedAdamW: {len(missing)} trainable parameter(s) are in no group (first: {missing[0]}); every "
+            raise ValueError(f"{self.NAME}: {len(missing)} trainable parameter(s) are in no group (first: {missing[0]}); every "
                              "parameter with requires_grad=True must be in exactly one group")
         self.store = store
         self.param_groups = out
         if len(out) > 1:
             self.chunk_group = slot_table(store, [g["param_names"] for g in out]).to(store.device)
-            n = 2 + 2 * len(out)        # allocated here, on the stream the optimiser is built on, not inside a step
+            n = self._group_hyper_floats(len(out))        # allocated here, on the stream the optimiser is built on, not inside a step
             cuda = torch.device(store.device).type == "cuda"
             self.group_hyper = torch.zeros(n, dtype=torch.float32, device=store.device)
             self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=store.device)
@@ -146,9 +189,7 @@ class FusedAdamW:
         self._group_stage_next = (self._group_stage_next + 1) % len(self._group_stage)
         if slot[1] is not None:
             slot[1].synchronize()
-        g0 = self.param_groups[0]
-        ops.adamw_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
-                                    g0["betas"][0], g0["betas"][1], self.step_count, slot[0])
+        self._fill_group_hyper(slot[0])
         table = self._group_hyper_behind if behind else self.group_hyper
         table.copy_(slot[0], non_blocking=True)
         if cuda:
@@ -156,13 +197,17 @@ class FusedAdamW:
             slot[1].record(torch.cuda.current_stream(dev))
         return table
 
-    def _adamw_groups(self, k: int, lo: int, hi: int, grad_scale: float, clip, table: Optional[torch.Tensor] = None) -> None:
-        """The grouped update of flat[lo:hi], a piece of trainable range ``k`` (lo a multiple of 64): one launch."""
-        st, g = self.store, self.param_groups[0]
-        m, v = self._moments(k, lo, hi)
-        ops.adamw_step_groups(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.chunk_group[lo // 64:],
-                              self.group_hyper if table is None else table, len(self.param_groups), g["betas"][0],
-                              g["betas"][1], g["eps"], grad_scale, clip, st.master_bf16[lo:hi])
+    def _update_piece(self, k: int, lo: int, hi: int, grad_scale: float, clip, table: Optional[torch.Tensor] = None,
+                      dev: bool = False) -> None:
+        """The update of flat[lo:hi], a piece of trainable range ``k`` (lo a multiple of 64): one launch, in the grouped form
+        with two or more groups, else with host scalars or (``dev``) device scalars."""
+        moments = self._moments(k, lo, hi)
+        if self.chunk_group is not None:
+            self._update_groups(lo, hi, moments, grad_scale, clip, self.group_hyper if table is None else table)
+        elif dev:
+            self._update_dev(lo, hi, moments, grad_scale, clip)
+        else:
+            self._update(lo, hi, moments, grad_scale, clip)
 
     def attach_exchange(self, exchange) -> None:
         """Data-parallel runs: hand the optimiser the gradient exchange of the process group.  With a
@@ -174,17 +219,18 @@ class FusedAdamW:
         if not isinstance(exchange, comm.ShardedGradExchange):
             self.exchange = None
             return
+        if not self.SHARDABLE:
+            raise ValueError(f"{self.NAME}: the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not supported; use the "
+                             "all-reduce exchange")
         if len(self.param_groups) > 1:
-            raise ValueError(f"FusedAdamW: {len(self.param_groups)} parameter groups with the sharded gradient exchange "
+            raise ValueError(f"{self.NAME}: {len(self.param_groups)} parameter groups with the sharded gradient exchange "
                              "(SC_GRAD_EXCHANGE=sharded) are not supported; use the all-reduce exchange")
         if self.store.locked:
-            raise ValueError("FusedAdamW: a locked tower with the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not "
+            raise ValueError(f"{self.NAME}: a locked tower with the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not "
                              "supported; use the all-reduce exchange")
         self.exchange = exchange
-        n = exchange.shard_floats()
+        self._alloc_state(exchange.shard_floats())
         dev = self.store.device
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self._partials = torch.zeros(1024 * len(exchange.buckets), dtype=torch.float64, device=dev)
 
     def _clip(self, grad_scale: float, max_norm: Optional[float], sumsq_partial: Optional[torch.Tensor]):
@@ -209,10 +255,9 @@ class FusedAdamW:
     def _moments(self, k: int, lo: int, hi: int):
         """Moment slices of flat[lo:hi], a piece of trainable range ``k``."""
         a = self._moff[k] + lo - self.ranges[k][0]
-        return self.exp_avg[a:a + hi - lo], self.exp_avg_sq[a:a + hi - lo]
+        return tuple(t[a:a + hi - lo] for t in self._state())
 
     def _step_sharded(self, grad_scale: float, max_norm: Optional[float]) -> torch.Tensor:
-        g = self.param_groups[0]
         st, ex = self.store, self.exchange
         st.wait_all()               # a step without a forward in between (tests): the previous gathers must have landed
         clip = None
@@ -231,9 +276,7 @@ class FusedAdamW:
             pos += b - a
         for k in ex.order:          # in the order the next forward consumes the buckets
             a, b = ex.piece(k)
-            m, v = self.exp_avg[off[k]:off[k] + (b - a)], self.exp_avg_sq[off[k]:off[k] + (b - a)]
-            ops.adamw_step(st.master[a:b], st.grad[a:b], m, v, b - a, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                           g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16[a:b])
+            self._update(a, b, tuple(t[off[k]:off[k] + (b - a)] for t in self._state()), grad_scale, clip)
             ex.gather_bucket(k)
         return self.norm_clip
 
@@ -268,10 +311,9 @@ class FusedAdamW:
         """The replicated update (one process, or the all-reduce route) bucket by bucket on the communication stream, in the order
         the next forward consumes the buckets: the forward waits per bucket at the first use of its parameters
         (``ParamStore.wait_names``, the mechanism of the sharded optimiser), so all but the first bucket of the HBM-bound update
-        (30 bytes per parameter) runs under the matrix-bound start of the next step.  Same kernels on the same values: weights
+        (AdamW: 30 bytes per parameter, Lion: 22) runs under the matrix-bound start of the next step.  Same kernels on the same values: weights
         bit-identical to the one-launch form (``SC_ADAMW_BEHIND=0``)."""
         from . import streams
-        g = self.param_groups[0]
         st = self.store
         st.wait_all()               # a step without a forward in between: the previous update must be complete
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
@@ -288,13 +330,7 @@ class FusedAdamW:
         with torch.cuda.stream(side):
             for k in order:
                 lo, hi = buckets[k]
-                if self.chunk_group is not None:
-                    self._adamw_groups(owner[k], lo, hi, grad_scale, clip, table)
-                else:
-                    m, v = self._moments(owner[k], lo, hi)
-                    ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"],
-                                   g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip,
-                                   st.master_bf16[lo:hi])
+                self._update_piece(owner[k], lo, hi, grad_scale, clip, table)
                 st.refresh_range(lo, hi, copies[k], plans[k], fresh=(lo, hi))
                 done = torch.cuda.Event()
                 done.record(side)
@@ -309,15 +345,7 @@ class FusedAdamW:
         if self.chunk_group is not None:
             self._refresh_group_hyper()
             return
-        g = self.param_groups[0]
-        if self.hyper is None:
-            self.hyper = torch.zeros(3, dtype=torch.float32, device=self.store.device)
-            self._hyper_host = torch.zeros(3, dtype=torch.float32).pin_memory()
-        # formed by the library itself, with the expressions of sc_adamw_step: same bits as the eager launch
-        from . import _lib
-        _lib.check(_lib.lib().sc_adamw_hyper_host(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), int(self.step_count),
-                                                  self._hyper_host.data_ptr()), "sc_adamw_hyper_host")
-        self.hyper.copy_(self._hyper_host, non_blocking=True)
+        self._refresh_scalar_hyper()
 
     def step_captured(self, grad_scale: float = 1.0, max_norm: Optional[float] = None,
                       sumsq_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -325,17 +353,11 @@ class FusedAdamW:
         scalars from device memory (``refresh_hyper``), no host-side step counter.  Single process only."""
         if self.exchange is not None:
             raise RuntimeError("step_captured: the sharded optimiser issues collectives; graph capture is single-process")
-        g = self.param_groups[0]
         st = self.store
         st.wait_all()
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
         for k, (lo, hi) in enumerate(self.ranges):
-            if self.chunk_group is not None:
-                self._adamw_groups(k, lo, hi, grad_scale, clip)
-                continue
-            m, v = self._moments(k, lo, hi)
-            ops.adamw_step_dev(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.hyper, g["betas"][0],
-                               g["betas"][1], g["eps"], g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
+            self._update_piece(k, lo, hi, grad_scale, clip, dev=True)
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -346,10 +368,9 @@ class FusedAdamW:
              sumsq_partial: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``sumsq_partial``: see ``_clip`` (accumulated steps of one process).  The replicated forms take it; the sharded
         optimiser forms its norm from per-shard partials and refuses it."""
-        g = self.param_groups[0]
         st = self.store
         if self.exchange is not None and sumsq_partial is not None:
-            raise ValueError("FusedAdamW.step: sumsq_partial= is for the replicated optimiser; the sharded exchange "
+            raise ValueError(f"{self.NAME}.step: sumsq_partial= is for the replicated optimiser; the sharded exchange "
                              "(SC_GRAD_EXCHANGE=sharded) computes its own per-shard partials")
         self.step_count += 1
         if self.exchange is not None:
@@ -364,12 +385,7 @@ class FusedAdamW:
         if self.chunk_group is not None:
             self._refresh_group_hyper()
         for k, (lo, hi) in enumerate(self.ranges):
-            if self.chunk_group is not None:
-                self._adamw_groups(k, lo, hi, grad_scale, clip)
-                continue
-            m, v = self._moments(k, lo, hi)
-            ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"], g["betas"][0],
-                           g["betas"][1], g["eps"], g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16[lo:hi])
+            self._update_piece(k, lo, hi, grad_scale, clip)
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -378,38 +394,151 @@ class FusedAdamW:
         sharded exchange this is a COLLECTIVE: every rank must call it (the trainer does, before rank 0 writes the file)."""
         self.store.wait_all()           # an update may still be running behind the forward (communication stream)
         if self.exchange is not None:
-            m, v = self.exchange.gather_moments(self.exp_avg), self.exchange.gather_moments(self.exp_avg_sq)
+            full = [self.exchange.gather_moments(t) for t in self._state()]
         elif self.ranges == [(0, self.store.total)]:
-            m, v = self.exp_avg.clone(), self.exp_avg_sq.clone()
+            full = [t.clone() for t in self._state()]
         else:       # the full flat layout, zeros in the locked ranges: the file resumes with or without the lock
-            m, v = self._expand(self.exp_avg), self._expand(self.exp_avg_sq)
-        return {"step": self.step_count, "exp_avg": m, "exp_avg_sq": v,
+            full = [self._expand(t) for t in self._state()]
+        return {**({} if self.KIND is None else {"optimizer": self.KIND}), "step": self.step_count, **dict(zip(self.STATE, full)),
                 "param_groups": [{k: v_ for k, v_ in g.items() if k != "params"} for g in self.param_groups]}
 
+    def _check_kind(self, sd) -> None:
+        """A checkpoint of the other optimiser kind is refused.  The kind is the "optimizer" entry; an AdamW file written before
+        that entry existed carries none and is known by its second moment."""
+        mine = self.KIND or "adamw"
+        has_sq = "exp_avg_sq" in sd
+        if sd.get("optimizer", "adamw" if has_sq else mine) != mine or has_sq != ("exp_avg_sq" in self.STATE):
+            other = "adamw" if mine == "lion" else "lion"
+            raise ValueError(f"{self.NAME}.load_state_dict: the state dict (keys {sorted(k for k in sd if k != 'param_groups')}) is "
+                             f"that of an {other!r} optimiser; this one is {mine!r} and keeps {list(self.STATE)}.  AdamW and Lion "
+                             "states do not convert into each other")
+
     def load_state_dict(self, sd) -> None:
+        self._check_kind(sd)
         self.store.wait_all()
         self.step_count = int(sd["step"])
         n = self.store.total
-        m, v = sd["exp_avg"], sd["exp_avg_sq"]
-        if m.numel() != n:          # a file written with another padding (other world size): the real parameters come first
-            keep = min(m.numel(), n)
-            m2, v2 = torch.zeros(n, dtype=m.dtype, device=m.device), torch.zeros(n, dtype=v.dtype, device=v.device)
-            m2[:keep], v2[:keep] = m[:keep], v[:keep]
-            m, v = m2, v2
+        full = [sd[name] for name in self.STATE]
+        for i, m in enumerate(full):
+            if m.numel() != n:      # a file written with another padding (other world size): the real parameters come first
+                keep = min(m.numel(), n)
+                m2 = torch.zeros(n, dtype=m.dtype, device=m.device)
+                m2[:keep] = m[:keep]
+                full[i] = m2
         if self.exchange is not None:
-            self.exchange.scatter_moments(m.to(self.exp_avg.device), self.exp_avg)
-            self.exchange.scatter_moments(v.to(self.exp_avg.device), self.exp_avg_sq)
+            for m, mine in zip(full, self._state()):
+                self.exchange.scatter_moments(m.to(mine.device), mine)
         else:       # the trainable slices of the full layout
             for k, (lo, hi) in enumerate(self.ranges):
-                dm, dv = self._moments(k, lo, hi)
-                dm.copy_(m[lo:hi])
-                dv.copy_(v[lo:hi])
+                for m, dm in zip(full, self._moments(k, lo, hi)):
+                    dm.copy_(m[lo:hi])
 
     def _expand(self, compact: torch.Tensor) -> torch.Tensor:
         full = torch.zeros(self.store.total, dtype=compact.dtype, device=compact.device)
         for k, (lo, hi) in enumerate(self.ranges):
             full[lo:hi] = compact[self._moff[k]:self._moff[k] + hi - lo]
         return full
+
+
+class FusedAdamW(_FlatOptimizer):
+    NAME = "FusedAdamW"
+    STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2):
+        super().__init__(params, lr, betas, eps, weight_decay)
+
+    def _update(self, lo, hi, moments, grad_scale, clip) -> None:
+        st, g = self.store, self.param_groups[0]
+        m, v = moments
+        ops.adamw_step(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                       g["weight_decay"], self.step_count, grad_scale, clip, st.master_bf16[lo:hi])
+
+    def _update_dev(self, lo, hi, moments, grad_scale, clip) -> None:
+        st, g = self.store, self.param_groups[0]
+        m, v = moments
+        ops.adamw_step_dev(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.hyper, g["betas"][0], g["betas"][1], g["eps"],
+                           g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
+
+    def _update_groups(self, lo, hi, moments, grad_scale, clip, table) -> None:
+        st, g = self.store, self.param_groups[0]
+        m, v = moments
+        ops.adamw_step_groups(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.chunk_group[lo // 64:], table,
+                              len(self.param_groups), g["betas"][0], g["betas"][1], g["eps"], grad_scale, clip,
+                              st.master_bf16[lo:hi])
+
+    def _refresh_scalar_hyper(self) -> None:
+        g = self.param_groups[0]
+        if self.hyper is None:
+            self.hyper = torch.zeros(3, dtype=torch.float32, device=self.store.device)
+            self._hyper_host = torch.zeros(3, dtype=torch.float32).pin_memory()
+        # formed by the library itself, with the expressions of sc_adamw_step: same bits as the eager launch
+        from . import _lib
+        _lib.check(_lib.lib().sc_adamw_hyper_host(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), int(self.step_count),
+                                                  self._hyper_host.data_ptr()), "sc_adamw_hyper_host")
+        self.hyper.copy_(self._hyper_host, non_blocking=True)
+
+    def _group_hyper_floats(self, n_groups: int) -> int:
+        return 2 + 2 * n_groups
+
+    def _fill_group_hyper(self, host: torch.Tensor) -> None:
+        g0 = self.param_groups[0]
+        ops.adamw_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
+                                    g0["betas"][0], g0["betas"][1], self.step_count, host)
+
+
+class FusedLion(_FlatOptimizer):
+    """Lion (Chen et al. 2023, Algorithm 1) with the keywords of ``lion_pytorch.Lion`` / ``timm.optim.Lion``: one moment
+    (4 bytes of state per parameter), ``p = p (1 - lr wd) - lr sign(b1 m + (1 - b1) g)``, ``m = b2 m + (1 - b2) g``, no bias
+    correction, no eps.  Parameter groups, locked towers, accumulation, the overlapped and the graph-captured step are
+    ``FusedAdamW``'s, on the same code; the sharded gradient exchange is refused.  The options of the two public classes that
+    change the update are accepted at their off value only."""
+    NAME = "FusedLion"
+    STATE = ("exp_avg",)
+    KIND = "lion"
+    SHARDABLE = False
+    GROUP_KEYS = tuple(k for k in _FlatOptimizer.GROUP_KEYS if k != "eps")
+    OFF_ONLY = {"use_triton": (False,), "decoupled_weight_decay": (False,), "caution": (False,), "maximize": (False,),
+                "foreach": (None, False)}
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4, betas=(0.9, 0.99), weight_decay: float = 0.0,
+                 **options):
+        for key, value in options.items():
+            if key not in self.OFF_ONLY:
+                raise ValueError(f"FusedLion: unknown keyword {key!r}; accepted: lr, betas, weight_decay and (off only) "
+                                 f"{list(self.OFF_ONLY)}")
+            if not any(value is off for off in self.OFF_ONLY[key]):
+                raise ValueError(f"FusedLion: {key}={value!r} is not supported; only {key}={self.OFF_ONLY[key][0]!r} (the plain "
+                                 "update of Algorithm 1 with decoupled weight decay) is")
+        super().__init__(params, lr, betas, None, weight_decay)
+
+    def _update(self, lo, hi, moments, grad_scale, clip) -> None:
+        st, g = self.store, self.param_groups[0]
+        ops.lion_step(st.master[lo:hi], st.grad[lo:hi], moments[0], hi - lo, g["lr"], g["betas"][0], g["betas"][1],
+                      g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
+
+    def _update_dev(self, lo, hi, moments, grad_scale, clip) -> None:
+        st, g = self.store, self.param_groups[0]
+        ops.lion_step_dev(st.master[lo:hi], st.grad[lo:hi], moments[0], hi - lo, self.hyper, g["betas"][0], g["betas"][1],
+                          g["weight_decay"], grad_scale, clip, st.master_bf16[lo:hi])
+
+    def _update_groups(self, lo, hi, moments, grad_scale, clip, table) -> None:
+        st, g = self.store, self.param_groups[0]
+        ops.lion_step_groups(st.master[lo:hi], st.grad[lo:hi], moments[0], hi - lo, self.chunk_group[lo // 64:], table,
+                             len(self.param_groups), g["betas"][0], g["betas"][1], grad_scale, clip, st.master_bf16[lo:hi])
+
+    def _refresh_scalar_hyper(self) -> None:
+        if self.hyper is None:
+            self.hyper = torch.zeros(1, dtype=torch.float32, device=self.store.device)
+            self._hyper_host = torch.zeros(1, dtype=torch.float32).pin_memory()
+        self._hyper_host[0] = float(self.param_groups[0]["lr"])       # rounded to fp32 as the host-scalar launch rounds it
+        self.hyper.copy_(self._hyper_host, non_blocking=True)
+
+    def _group_hyper_floats(self, n_groups: int) -> int:
+        return 2 * n_groups
+
+    def _fill_group_hyper(self, host: torch.Tensor) -> None:
+        ops.lion_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups], host)
 
 
 def slot_table(store, group_names: Sequence[Sequence[str]]) -> torch.Tensor:
