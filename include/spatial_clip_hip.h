@@ -524,6 +524,35 @@ int sc_lion_groups_hyper_host(const float* lr, const float* wd, int n_groups, fl
 int sc_lion_step_groups(float* params, const float* grads, float* exp_avg, long long n, const unsigned char* chunk_group,
                         const float* group_hyper, int n_groups, float beta1, float beta2, float grad_scale,
                         const float* norm_clip, void* params_bf16, void* stream);
+/* LAMB (You et al. 2020; timm.optim.Lamb with its defaults -- open_clip's `--opt timm/lamb`) over the same flat buffers.
+ * Per tensor T (one parameter of the store) with {lr_T, wd_T}, for ge = g * grad_scale * clip:
+ *   m = beta1 m + (1 - beta1) ge;   v = beta2 v + (1 - beta2) ge^2
+ *   u = (m / (1 - beta1^t)) / (sqrt(v) / sqrt(1 - beta2^t) + eps) + wd_T p
+ *   r = ||p|| / ||u|| over T where both norms are positive, else 1; 1 where wd_T == 0 unless always_adapt; min(r, 1) under
+ *   trust_clip;   p = p - lr_T r u
+ * One step is three kinds of launch, and the bits of p, m, v, r do not depend on how the buffer is cut into ranges:
+ *   sc_lamb_moments  over a range of n floats (whole 64-float slots): updates m, v and leaves {sum p^2, sum u^2} of every
+ *                    slot of the range in slot_sums (2 floats per slot, the range's first slot first);
+ *   sc_lamb_trust    once, after every range: sums each tensor's slots in fp64 in a fixed order and writes trust[T];
+ *                    slot_sums / n_slots are the WHOLE buffer's, tensor_slots (DEVICE ints) = {first slot, one past the last}
+ *                    per tensor;
+ *   sc_lamb_apply    over a range: forms u again from (p, m, v) with the expression of sc_lamb_moments, applies the step and
+ *                    writes the bf16 mirror (may be NULL).
+ * slot_tensor (DEVICE ints, one per slot of the range) names the tensor of each slot; a slot with a negative entry or one
+ * >= n_tensors is neither read nor written.  hyper (DEVICE, 2 + 2 * n_tensors floats) = {1 - beta1^step,
+ * sqrt(1 - beta2^step)}, then {lr_T, wd_T} per tensor: sc_lamb_hyper_host fills a HOST copy from per-group scalars and
+ * tensor_group (HOST ints, the group of each tensor), the bias corrections with sc_adamw_step's expressions.  n: a positive
+ * multiple of 64; 1 <= n_groups <= 256; 1 <= n_tensors <= 2^20; fp32 buffers 16-byte aligned.  No atomics.  A refusal sets
+ * sc_last_error and launches nothing. */
+int sc_lamb_hyper_host(const float* lr, const float* wd, int n_groups, const int* tensor_group, int n_tensors, float beta1,
+                       float beta2, int step, float* out_host);
+int sc_lamb_moments(const float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                    const int* slot_tensor, const float* hyper, int n_tensors, float beta1, float beta2, float eps,
+                    float grad_scale, const float* norm_clip, float* slot_sums, void* stream);
+int sc_lamb_trust(const float* slot_sums, long long n_slots, const int* tensor_slots, const float* hyper, int n_tensors,
+                  int always_adapt, int trust_clip, float* trust, void* stream);
+int sc_lamb_apply(float* params, const float* exp_avg, const float* exp_avg_sq, long long n, const int* slot_tensor,
+                  const float* hyper, const float* trust, int n_tensors, float eps, void* params_bf16, void* stream);
 /* The two halves of sc_grad_norm for an optimiser that owns 1/W of every gradient bucket (reduce-scatter ->
  * AdamW on the rank's shard -> all-gather; Lightning's DDP mean, configs/trainer/ddp.yaml:4, replaced): 1024 fp64 partial
  * sums of squares per contiguous piece of the shard, then -- after the caller has all-reduced (SUM) the concatenated

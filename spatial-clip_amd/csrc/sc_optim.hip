@@ -208,6 +208,155 @@ __global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const 
     }
 }
 
+// ---- LAMB (You et al. 2020; timm.optim.Lamb with its defaults, open_clip's `--opt timm/lamb`): Adam's moments, then a
+// layer-wise trust ratio.  Per tensor T with {lr_T, wd_T}, for ge = g * grad_scale * clip:
+//   m = b1 m + (1 - b1) ge;   v = b2 v + (1 - b2) ge^2
+//   u = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd_T p
+//   r = ||p|| / ||u|| over T where both norms are positive, else 1 (and 1 where wd_T == 0 unless always_adapt);  p -= lr_T r u
+// The update of an element depends on two norms over its whole tensor, and the flat buffers are cut into pieces that ignore
+// tensor boundaries (buckets, trainable ranges, grid-stride trips).  So the reduction is segmented by the 64-float SLOT, the
+// unit no cut divides: lamb_moments_kernel leaves {sum p^2, sum u^2} of every slot in a slot-indexed buffer, lamb_trust_kernel
+// sums each tensor's slots, lamb_apply_kernel forms u again from (p, m, v) and applies the step.  A slot's pair depends on its
+// 64 values alone, in a fixed order; a tensor's sums on its slots alone, in a fixed order; there are no atomics.  The bits are
+// therefore the same however the buffer is cut and in whatever order the pieces are launched.
+//   hyper (DEVICE) = {1 - b1^t, sqrt(1 - b2^t)}, then {lr_T, wd_T} per tensor (sc_lamb_hyper_host)
+//   slot_tensor[slot] = the tensor of a slot, negative where the slot belongs to none (padding behind the last parameter, a
+//   locked parameter): such a slot is neither read nor written.  32 bits wide: ViT-H + text has more than 256 tensors.
+// u is formed by ONE function with explicit fmaf / division / sqrtf and no contractible product-sum, so that both kernels
+// form the same bits from the same (p, m, v) whatever surrounds the call.  Slot padding (p = g = m = v = 0) gives u = 0.
+SC_DEVICE float lamb_u(float p, float m, float v, float wd, float bc1, float bc2_sqrt, float eps) {
+    return fmaf(wd, p, (m / bc1) / (sqrtf(v) / bc2_sqrt + eps));
+}
+
+// 42 bytes per parameter over the two streaming kernels: 16 read + 8 written here, 12 read + 6 written in lamb_apply_kernel.
+// float4 i belongs to slot i >> 4, so the 16 lanes [16 k, 16 k + 16) of a wave hold one slot (the block starts on a multiple
+// of 256 float4); n is a multiple of 64, so a slot's lanes enter and leave the loop together.
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long long n,
+                                                           const int* __restrict__ slot_tensor, const float* __restrict__ hyper,
+                                                           int n_tensors, float b1, float b2, float eps, float gscale,
+                                                           const float* __restrict__ normclip, float2* __restrict__ slot_sums) {
+    const float bc1 = hyper[0], bc2_sqrt = hyper[1];
+    const float gs = gscale * (normclip ? normclip[1] : 1.0f);
+    const long long n4 = n >> 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int t = slot_tensor[i >> 4];
+        if (t < 0 || t >= n_tensors) continue;
+        const float wd = hyper[3 + 2 * t];
+        const f32x4 pp = reinterpret_cast<const f32x4*>(p)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+        float pq[4], uq[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float ge = gg[c] * gs;
+            mm[c] = b1 * mm[c] + (1.0f - b1) * ge;
+            vv[c] = b2 * vv[c] + (1.0f - b2) * ge * ge;
+            const float u = lamb_u(pp[c], mm[c], vv[c], wd, bc1, bc2_sqrt, eps);
+            pq[c] = pp[c] * pp[c];
+            uq[c] = u * u;
+        }
+        float sp = (pq[0] + pq[1]) + (pq[2] + pq[3]);
+        float su = (uq[0] + uq[1]) + (uq[2] + uq[3]);
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {       // butterfly over the slot's 16 lanes: every lane ends with the same bits
+            sp += __shfl_xor(sp, o, 64);
+            su += __shfl_xor(su, o, 64);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mm;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+        if ((threadIdx.x & 15) == 0) slot_sums[i >> 4] = make_float2(sp, su);
+    }
+}
+
+// One block of 1024 threads per tensor: its slots' pairs summed in fp64.  Thread k takes slots first + k, first + k + 1024, ...
+// in turn, four at a time into four chains (four loads in flight: the largest tensor of configs[1] has 160 000 slots and its
+// block is what the launch waits for), the rest into the first chain; then the chains, the wave butterfly and the sixteen
+// waves in order.  tensor_slots = {first slot, one past the last} per tensor; a pair outside [0, n_slots] is not followed
+// (r = 1).
+__global__ __launch_bounds__(1024) void lamb_trust_kernel(const float2* __restrict__ slot_sums, long long n_slots,
+                                                          const int* __restrict__ tensor_slots, const float* __restrict__ hyper,
+                                                          int always_adapt, int trust_clip, float* __restrict__ trust) {
+    __shared__ double sm[2][16];
+    const int t = blockIdx.x;
+    const long long first = tensor_slots[2 * t], end = tensor_slots[2 * t + 1];
+    const bool ok = first >= 0 && first <= end && end <= n_slots;
+    double p4[4] = {0.0, 0.0, 0.0, 0.0}, u4[4] = {0.0, 0.0, 0.0, 0.0};
+    if (ok) {
+        long long s = first + threadIdx.x;
+        for (; s + 3 * 1024 < end; s += 4 * 1024) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float2 q = slot_sums[s + k * 1024];
+                p4[k] += (double)q.x;
+                u4[k] += (double)q.y;
+            }
+        }
+        for (; s < end; s += 1024) {
+            const float2 q = slot_sums[s];
+            p4[0] += (double)q.x;
+            u4[0] += (double)q.y;
+        }
+    }
+    double sp = (p4[0] + p4[1]) + (p4[2] + p4[3]);
+    double su = (u4[0] + u4[1]) + (u4[2] + u4[3]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sp += __shfl_xor(sp, o, 64);
+        su += __shfl_xor(su, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sm[0][threadIdx.x >> 6] = sp;
+        sm[1][threadIdx.x >> 6] = su;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tp = 0.0, tu = 0.0;
+        for (int w = 0; w < 16; ++w) {
+            tp += sm[0][w];
+            tu += sm[1][w];
+        }
+        const double pn = sqrt(tp), un = sqrt(tu);
+        const float wd = hyper[3 + 2 * t];
+        float r = 1.0f;
+        if (ok && (always_adapt || wd != 0.0f) && pn > 0.0 && un > 0.0) r = (float)(pn / un);
+        if (trust_clip) r = fminf(r, 1.0f);
+        trust[t] = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m,
+                                                         const float* __restrict__ v, long long n,
+                                                         const int* __restrict__ slot_tensor, const float* __restrict__ hyper,
+                                                         const float* __restrict__ trust, int n_tensors, float eps,
+                                                         bf16* __restrict__ pbf) {
+    const float bc1 = hyper[0], bc2_sqrt = hyper[1];
+    const long long n4 = n >> 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+         i += (long long)gridDim.x * blockDim.x) {
+        const int t = slot_tensor[i >> 4];
+        if (t < 0 || t >= n_tensors) continue;
+        const float lr = hyper[2 + 2 * t], wd = hyper[3 + 2 * t];
+        const float step = lr * trust[t];
+        f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+        const f32x4 mm = reinterpret_cast<const f32x4*>(m)[i];
+        const f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float u = lamb_u(pp[c], mm[c], vv[c], wd, bc1, bc2_sqrt, eps);
+            pp[c] -= step * u;
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pp;
+        if (pbf) {      // bf16 mirror of the master buffer, as adamw_kernel writes it
+            bf16x4 o;
+            o[0] = (bf16)pp[0]; o[1] = (bf16)pp[1]; o[2] = (bf16)pp[2]; o[3] = (bf16)pp[3];
+            reinterpret_cast<bf16x4*>(pbf)[i] = o;
+        }
+    }
+}
+
 // ---- gradient accumulation (Trainer accumulate_grad_batches): every backward OVERWRITES the flat gradient buffer, so the
 // sum over the micro-batches of a group is a running fp32 buffer beside it, folded once per micro-batch by this kernel:
 //   mode 0 (first)  acc   = scale * grads
@@ -496,6 +645,77 @@ extern "C" int sc_lion_step_groups(float* params, const float* grads, float* exp
     lion_kernel<true><<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, n, 0.f, 0.f, beta1, beta2, grad_scale,
                                                                       norm_clip, (bf16*)params_bf16, nullptr, chunk_group,
                                                                       group_hyper, n_groups);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- LAMB: the three kernels of one step and the host function that fills their scalar table.  One form for the eager
+// and the graph-captured step, for one group and for many: the table carries every tensor's {lr, wd}.  A refusal launches
+// nothing.
+static inline bool lamb_aligned16(const void* a, const void* b, const void* c, const void* d) {
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
+}
+
+extern "C" int sc_lamb_hyper_host(const float* lr, const float* wd, int n_groups, const int* tensor_group, int n_tensors,
+                                  float beta1, float beta2, int step, float* out_host) {
+    SC_CHECK(lr != nullptr && wd != nullptr && tensor_group != nullptr && out_host != nullptr,
+             "sc_lamb_hyper_host: lr, wd, tensor_group and the host output are required");
+    SC_CHECK(n_groups >= 1 && n_groups <= 256, "sc_lamb_hyper_host: n_groups = %d (1 .. 256)", n_groups);
+    SC_CHECK(n_tensors >= 1 && n_tensors <= (1 << 20), "sc_lamb_hyper_host: n_tensors = %d (1 .. 2^20)", n_tensors);
+    SC_CHECK(step >= 1, "sc_lamb_hyper_host: step = %d (>= 1)", step);
+    for (int k = 0; k < n_tensors; ++k)
+        SC_CHECK(tensor_group[k] >= 0 && tensor_group[k] < n_groups, "sc_lamb_hyper_host: tensor %d names group %d of %d", k,
+                 tensor_group[k], n_groups);
+    adamw_bias_corrections(beta1, beta2, step, out_host, out_host + 1);
+    for (int k = 0; k < n_tensors; ++k) {
+        out_host[2 + 2 * k] = lr[tensor_group[k]];
+        out_host[3 + 2 * k] = wd[tensor_group[k]];
+    }
+    return 0;
+}
+
+extern "C" int sc_lamb_moments(const float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                               const int* slot_tensor, const float* hyper, int n_tensors, float beta1, float beta2, float eps,
+                               float grad_scale, const float* norm_clip, float* slot_sums, void* stream) {
+    SC_CHECK(n > 0 && (n % 64) == 0, "sc_lamb_moments: n = %lld must be a positive multiple of 64 (whole slots)", n);
+    SC_CHECK(n_tensors >= 1 && n_tensors <= (1 << 20), "sc_lamb_moments: n_tensors = %d (1 .. 2^20)", n_tensors);
+    SC_CHECK(params && grads && exp_avg && exp_avg_sq, "sc_lamb_moments: params, grads and both moments are required");
+    SC_CHECK(slot_tensor != nullptr && hyper != nullptr && slot_sums != nullptr,
+             "sc_lamb_moments: slot_tensor, hyper and slot_sums are required");
+    SC_CHECK(lamb_aligned16(params, grads, exp_avg, exp_avg_sq) && (((uintptr_t)slot_sums) & 7) == 0,
+             "sc_lamb_moments: the buffers must be 16-byte aligned, slot_sums 8-byte aligned");
+    lamb_moments_kernel<<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, slot_tensor, hyper,
+                                                                        n_tensors, beta1, beta2, eps, grad_scale, norm_clip,
+                                                                        (float2*)slot_sums);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+// slot_sums: n_slots {sum p^2, sum u^2} pairs; tensor_slots (DEVICE): {first slot, one past the last} per tensor, inside
+// [0, n_slots]; trust: n_tensors floats.
+extern "C" int sc_lamb_trust(const float* slot_sums, long long n_slots, const int* tensor_slots, const float* hyper, int n_tensors,
+                             int always_adapt, int trust_clip, float* trust, void* stream) {
+    SC_CHECK(n_slots > 0 && n_slots <= 0x7fffffffLL, "sc_lamb_trust: n_slots = %lld (1 .. 2^31 - 1)", n_slots);
+    SC_CHECK(n_tensors >= 1 && n_tensors <= (1 << 20), "sc_lamb_trust: n_tensors = %d (1 .. 2^20)", n_tensors);
+    SC_CHECK(slot_sums != nullptr && tensor_slots != nullptr && hyper != nullptr && trust != nullptr,
+             "sc_lamb_trust: slot_sums, tensor_slots, hyper and trust are required");
+    SC_CHECK((((uintptr_t)slot_sums) & 7) == 0, "sc_lamb_trust: slot_sums must be 8-byte aligned");
+    lamb_trust_kernel<<<n_tensors, 1024, 0, (hipStream_t)stream>>>((const float2*)slot_sums, n_slots, tensor_slots, hyper,
+                                                                 always_adapt, trust_clip, trust);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sc_lamb_apply(float* params, const float* exp_avg, const float* exp_avg_sq, long long n, const int* slot_tensor,
+                             const float* hyper, const float* trust, int n_tensors, float eps, void* params_bf16, void* stream) {
+    SC_CHECK(n > 0 && (n % 64) == 0, "sc_lamb_apply: n = %lld must be a positive multiple of 64 (whole slots)", n);
+    SC_CHECK(n_tensors >= 1 && n_tensors <= (1 << 20), "sc_lamb_apply: n_tensors = %d (1 .. 2^20)", n_tensors);
+    SC_CHECK(params && exp_avg && exp_avg_sq, "sc_lamb_apply: params and both moments are required");
+    SC_CHECK(slot_tensor != nullptr && hyper != nullptr && trust != nullptr, "sc_lamb_apply: slot_tensor, hyper and trust are required");
+    SC_CHECK(lamb_aligned16(params, exp_avg, exp_avg_sq, nullptr) && (((uintptr_t)params_bf16) & 7) == 0,
+             "sc_lamb_apply: the buffers must be 16-byte aligned, the bf16 mirror 8-byte aligned");
+    lamb_apply_kernel<<<lion_blocks(n), 256, 0, (hipStream_t)stream>>>(params, exp_avg, exp_avg_sq, n, slot_tensor, hyper, trust,
+                                                                      n_tensors, eps, (bf16*)params_bf16);
     SC_LAUNCH_CHECK();
     return 0;
 }

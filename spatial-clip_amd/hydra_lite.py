@@ -37,6 +37,8 @@ TARGET_MAP = {
     "lion_pytorch.Lion": "spatial_clip_amd.optim.FusedLion",
     "timm.optim.Lion": "spatial_clip_amd.optim.FusedLion",
     "timm.optim.lion.Lion": "spatial_clip_amd.optim.FusedLion",
+    "timm.optim.Lamb": "spatial_clip_amd.optim.FusedLamb",
+    "timm.optim.lamb.Lamb": "spatial_clip_amd.optim.FusedLamb",
     "transformers.get_cosine_schedule_with_warmup": "spatial_clip_amd.optim.get_cosine_schedule_with_warmup",
     "lightning.pytorch.Trainer": "spatial_clip_amd.trainer.Trainer",
     "lightning.Trainer": "spatial_clip_amd.trainer.Trainer",

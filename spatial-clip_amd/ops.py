@@ -920,6 +920,78 @@ def lion_step_groups(p, g, m, n, chunk_group, group_hyper, n_groups, beta1, beta
                                          _stream()), "sc_lion_step_groups")
 
 
+def _lamb_tables(what, n_slots, n_tensors, slot_tensor=None, hyper=None, trust=None, slot_sums=None, tensor_slots=None):
+    """Dtype, device and size of the LAMB tables that are given (``None`` is passed on as NULL, which the library refuses)."""
+    ok = 1 <= n_tensors <= (1 << 20)        # outside: the library refuses before anything is read
+    for t, dtype, name, need in ((slot_tensor, torch.int32, "slot_tensor", n_slots), (hyper, torch.float32, "hyper", 2 + 2 * n_tensors),
+                                 (trust, torch.float32, "trust", n_tensors), (slot_sums, torch.float32, "slot_sums", 2 * n_slots),
+                                 (tensor_slots, torch.int32, "tensor_slots", 2 * n_tensors)):
+        if t is None:
+            continue
+        _req(t, dtype, name)
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if ok and n_slots > 0 and t.numel() < need:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, {need} are needed")
+
+
+def lamb_hyper_host(lr, wd, tensor_group, beta1, beta2, step, out_host):
+    """Fill the HOST fp32 tensor ``out_host`` (2 + 2 * len(tensor_group) floats, pinned for an async copy) with
+    {1 - beta1^step, sqrt(1 - beta2^step)} and then {lr, wd} of every tensor's group: what the ``lamb_*`` launches read from its
+    device copy.  ``lr`` / ``wd``: one per group; ``tensor_group``: int32 host tensor, the group of each tensor."""
+    n_groups, n_tensors = len(lr), int(tensor_group.numel())
+    if len(wd) != n_groups:
+        raise ValueError(f"lamb_hyper_host: {n_groups} learning rates, {len(wd)} weight decays")
+    if tensor_group.is_cuda or tensor_group.dtype != torch.int32 or not tensor_group.is_contiguous():
+        raise ValueError("lamb_hyper_host: tensor_group must be contiguous int32 in host memory")
+    if out_host.is_cuda or out_host.dtype != torch.float32 or not out_host.is_contiguous() or out_host.numel() < 2 + 2 * n_tensors:
+        raise ValueError(f"lamb_hyper_host: out_host must be {2 + 2 * n_tensors} contiguous float32 in host memory")
+    arr = ctypes.c_float * max(n_groups, 1)
+    check(_lib.lib().sc_lamb_hyper_host(arr(*[float(x) for x in lr]), arr(*[float(x) for x in wd]), n_groups,
+                                        tensor_group.data_ptr(), n_tensors, float(beta1), float(beta2), int(step),
+                                        out_host.data_ptr()), "sc_lamb_hyper_host")
+    return out_host
+
+
+def lamb_moments(p, g, m, v, n, slot_tensor, hyper, n_tensors, beta1, beta2, eps, grad_scale, norm_clip, slot_sums):
+    """LAMB, first pass over flat[:n] (``sc_lamb_moments``): Adam's moments, and {sum p^2, sum u^2} of every 64-float slot into
+    ``slot_sums`` (fp32, 2 per slot).  ``slot_tensor`` (int32, one per slot) names each slot's tensor, ``hyper`` is
+    ``lamb_hyper_host``'s layout on the device.  p is not written."""
+    n, n_tensors = int(n), int(n_tensors)
+    _lamb_tables("lamb_moments", n // 64, n_tensors, slot_tensor=slot_tensor, hyper=hyper, slot_sums=slot_sums)
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"lamb_moments: {name} holds {t.numel()} floats, n = {n}")
+    check(_lib.lib().sc_lamb_moments(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, _ptr(slot_tensor), _ptr(hyper),
+                                     n_tensors, float(beta1), float(beta2), float(eps), float(grad_scale), _ptr(norm_clip),
+                                     _ptr(slot_sums), _stream()), "sc_lamb_moments")
+
+
+def lamb_trust(slot_sums, n_slots, tensor_slots, hyper, n_tensors, always_adapt, trust_clip, trust):
+    """LAMB, between the passes (``sc_lamb_trust``): ``trust[T]`` from the slot sums of the WHOLE buffer (``n_slots`` pairs);
+    ``tensor_slots`` (int32, 2 per tensor): first slot and one past the last."""
+    n_slots, n_tensors = int(n_slots), int(n_tensors)
+    _lamb_tables("lamb_trust", n_slots, n_tensors, hyper=hyper, trust=trust, slot_sums=slot_sums, tensor_slots=tensor_slots)
+    check(_lib.lib().sc_lamb_trust(_ptr(slot_sums), n_slots, _ptr(tensor_slots), _ptr(hyper), n_tensors, int(bool(always_adapt)),
+                                   int(bool(trust_clip)), _ptr(trust), _stream()), "sc_lamb_trust")
+
+
+def lamb_apply(p, m, v, n, slot_tensor, hyper, trust, n_tensors, eps, p_bf16=None):
+    """LAMB, second pass over flat[:n] (``sc_lamb_apply``): ``p -= lr_T * trust[T] * u`` with u formed again from (p, m, v); the
+    bf16 mirror is written when given."""
+    n, n_tensors = int(n), int(n_tensors)
+    _lamb_tables("lamb_apply", n // 64, n_tensors, slot_tensor=slot_tensor, hyper=hyper, trust=trust)
+    for t, name in ((p, "p"), (m, "m"), (v, "v")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"lamb_apply: {name} holds {t.numel()} floats, n = {n}")
+    if p_bf16 is not None and p_bf16.numel() < n:
+        raise ValueError(f"lamb_apply: the bf16 mirror holds {p_bf16.numel()} elements, n = {n}")
+    check(_lib.lib().sc_lamb_apply(p.data_ptr(), m.data_ptr(), v.data_ptr(), n, _ptr(slot_tensor), _ptr(hyper), _ptr(trust),
+                                   n_tensors, float(eps), _ptr(p_bf16), _stream()), "sc_lamb_apply")
+
+
 def cast_transpose_batched(master, desc, tile_prefix, n, total_tiles, mirror_bf16=None):
     check(_lib.lib().sc_cast_transpose_batched(master.data_ptr(), _ptr(mirror_bf16), desc.data_ptr(),
                                                tile_prefix.data_ptr(), n, total_tiles, _stream()),

@@ -8,7 +8,8 @@ bf16 compute-copy refresh.  ``params`` may also be torch's other form, a list of
 "weight_decay": ...}`` dicts (``open_clip_param_groups``, ``scaled_lr_groups``): with two or more groups every step form
 launches ``ops.adamw_step_groups``, one streaming launch per range with a per-slot group table.
 ``FusedLion(params, lr, betas, weight_decay)`` takes the kwargs of ``lion_pytorch.Lion`` / ``timm.optim.Lion`` and runs the
-same step forms with one moment (``ops.lion_step*``); both are ``_FlatOptimizer`` with their own launches.
+same step forms with one moment (``ops.lion_step*``); ``FusedLamb`` takes the kwargs of ``timm.optim.Lamb``
+and runs them with per-tensor trust ratios (``ops.lamb_*``, section 4m); all three are ``_FlatOptimizer`` with their own launches.
 ``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
 (configs/scheduler/cosine.yaml): the first optimiser step runs with lr = 0."""
 from __future__ import annotations
@@ -109,6 +110,18 @@ class _FlatOptimizer:
         """Two or more groups: the same for every group into the pinned HOST tensor ``host``."""
         raise NotImplementedError
 
+    def _uses_table(self) -> bool:
+        """The launches read a device table of scalars (``group_hyper``): with two or more groups."""
+        return self.chunk_group is not None
+
+    def _clip_threshold(self, max_norm: Optional[float]) -> Optional[float]:
+        """The threshold ``_clip`` clips at, from the ``max_norm`` a step form was called with."""
+        return max_norm
+
+    def _before_pieces(self, grad_scale: float, clip, table: Optional[torch.Tensor]) -> None:
+        """Launches of a step that must cover EVERY trainable range before the first ``_update_piece`` (LAMB: the moments and
+        the per-tensor trust ratios), on the stream of the pieces; ``table`` as in ``_update_piece``."""
+
     # ---- parameter groups
     GROUP_KEYS = ("params", "lr", "weight_decay", "betas", "eps", "initial_lr", "param_names")
     MAX_GROUPS = 256        # the slot table holds one byte per slot, the kernel 256 {decay, step} pairs in LDS
@@ -202,7 +215,7 @@ class _FlatOptimizer:
         """The update of flat[lo:hi], a piece of trainable range ``k`` (lo a multiple of 64): one launch, in the grouped form
         with two or more groups, else with host scalars or (``dev``) device scalars."""
         moments = self._moments(k, lo, hi)
-        if self.chunk_group is not None:
+        if self._uses_table():
             self._update_groups(lo, hi, moments, grad_scale, clip, self.group_hyper if table is None else table)
         elif dev:
             self._update_dev(lo, hi, moments, grad_scale, clip)
@@ -237,6 +250,7 @@ class _FlatOptimizer:
         """The clip coefficient of the replicated forms (None: no clipping).  ``sumsq_partial``: 1024 fp64 partial sums of squares
         of the gradient, left by the pass that formed it (``GradAccumulator.fold`` of a group's last micro-batch): the norm is
         finished from them and the gradient is not read a second time."""
+        max_norm = self._clip_threshold(max_norm)
         if max_norm is None or max_norm <= 0:
             return None
         st = self.store
@@ -321,13 +335,14 @@ class _FlatOptimizer:
         cur = torch.cuda.current_stream(st.device)
         side = streams.comm_stream(st.device)       # (a low-priority stream of its own measured the same on ViT-B/16, worse on ViT-L/14)
         table = None
-        if self.chunk_group is not None:
+        if self._uses_table():
             with torch.cuda.stream(side):   # in front of the wait for the backward: behind the last update in stream order only
                 table = self._refresh_group_hyper(behind=True)
         ready = torch.cuda.Event()
         ready.record(cur)
         side.wait_event(ready)
         with torch.cuda.stream(side):
+            self._before_pieces(grad_scale, clip, table)
             for k in order:
                 lo, hi = buckets[k]
                 self._update_piece(owner[k], lo, hi, grad_scale, clip, table)
@@ -342,7 +357,7 @@ class _FlatOptimizer:
         """Write {lr, 1 - beta1^step, sqrt(1 - beta2^step)} for the step about to run (``step_count`` already advanced) into
         the device triple ``self.hyper``: one 12-byte async H2D copy on the current stream, enqueued in front of the graph
         replay that reads it.  With two or more parameter groups: the group table ``self.group_hyper`` instead."""
-        if self.chunk_group is not None:
+        if self._uses_table():
             self._refresh_group_hyper()
             return
         self._refresh_scalar_hyper()
@@ -356,6 +371,7 @@ class _FlatOptimizer:
         st = self.store
         st.wait_all()
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
+        self._before_pieces(grad_scale, clip, None)
         for k, (lo, hi) in enumerate(self.ranges):
             self._update_piece(k, lo, hi, grad_scale, clip, dev=True)
         st.refresh_compute_copies(mirror_is_fresh=True)
@@ -382,8 +398,9 @@ class _FlatOptimizer:
         if st.master.is_cuda and (behind == "1" or (behind not in ("0", "1") and st.total <= 200_000_000)):
             return self._step_behind_forward(grad_scale, max_norm, sumsq_partial)
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
-        if self.chunk_group is not None:
+        if self._uses_table():
             self._refresh_group_hyper()
+        self._before_pieces(grad_scale, clip, None)
         for k, (lo, hi) in enumerate(self.ranges):
             self._update_piece(k, lo, hi, grad_scale, clip)
         st.refresh_compute_copies(mirror_is_fresh=True)
@@ -403,14 +420,16 @@ class _FlatOptimizer:
                 "param_groups": [{k: v_ for k, v_ in g.items() if k != "params"} for g in self.param_groups]}
 
     def _check_kind(self, sd) -> None:
-        """A checkpoint of the other optimiser kind is refused.  The kind is the "optimizer" entry; an AdamW file written before
-        that entry existed carries none and is known by its second moment."""
+        """A checkpoint of another optimiser kind ("adamw", "lion", "lamb") is refused.  The kind is the "optimizer" entry; an
+        AdamW file carries none (it was written before that entry existed, and still is) and is known by its second moment."""
         mine = self.KIND or "adamw"
         has_sq = "exp_avg_sq" in sd
-        if sd.get("optimizer", "adamw" if has_sq else mine) != mine or has_sq != ("exp_avg_sq" in self.STATE):
-            other = "adamw" if mine == "lion" else "lion"
+        theirs = sd.get("optimizer", "adamw" if has_sq else "lion")
+        if theirs != mine or has_sq != ("exp_avg_sq" in self.STATE):
+            other = theirs if theirs != mine else ("adamw" if has_sq else "lion")
+            kinds = "AdamW and Lion" if {mine, other} == {"adamw", "lion"} else "AdamW, Lion and LAMB"
             raise ValueError(f"{self.NAME}.load_state_dict: the state dict (keys {sorted(k for k in sd if k != 'param_groups')}) is "
-                             f"that of an {other!r} optimiser; this one is {mine!r} and keeps {list(self.STATE)}.  AdamW and Lion "
+                             f"that of an {other!r} optimiser; this one is {mine!r} and keeps {list(self.STATE)}.  {kinds} "
                              "states do not convert into each other")
 
     def load_state_dict(self, sd) -> None:
@@ -539,6 +558,105 @@ class FusedLion(_FlatOptimizer):
 
     def _fill_group_hyper(self, host: torch.Tensor) -> None:
         ops.lion_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups], host)
+
+
+class FusedLamb(_FlatOptimizer):
+    """LAMB (You et al. 2020) with the keywords and defaults of ``timm.optim.Lamb``: Adam's moments, then per tensor -- one
+    parameter of the store -- the trust ratio ``r = ||p|| / ||u||`` of ``u = m_hat / (sqrt(v_hat) + eps) + wd p`` and
+    ``p -= lr r u``.  A tensor of a group without weight decay gets ``r = 1`` unless ``always_adapt``; ``trust_clip`` caps r at 1.
+    timm's built-in clip (``max_grad_norm``) and the Trainer's ``gradient_clip_val`` compose to ONE clip at the smaller
+    threshold, which is what runs (``_clip_threshold``).  A step is ``ops.lamb_moments`` over every trainable range,
+    ``ops.lamb_trust`` once, ``ops.lamb_apply`` over the pieces of the step form; one group or many are the
+    same launches, the device table carries every tensor's {lr, wd}.  Parameter groups, locked towers, accumulation, the
+    overlapped and the graph-captured step are ``FusedAdamW``'s, on the same code; the sharded gradient exchange is refused."""
+    NAME = "FusedLamb"
+    STATE = ("exp_avg", "exp_avg_sq")
+    KIND = "lamb"
+    SHARDABLE = False
+    ON_ONLY = ("bias_correction", "grad_averaging")
+    OFF_ONLY = {"caution": (False,), "decoupled_decay": (False,), "maximize": (False,), "foreach": (None, False)}
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = 1.0, trust_clip: bool = False,
+                 always_adapt: bool = False, **options):
+        for key, value in options.items():
+            if key in self.ON_ONLY:
+                if value is not True:
+                    raise ValueError(f"FusedLamb: {key}={value!r} is not supported; only {key}=True (timm's default) is")
+            elif key not in self.OFF_ONLY:
+                raise ValueError(f"FusedLamb: unknown keyword {key!r}; accepted: lr, betas, eps, weight_decay, max_grad_norm, "
+                                 f"trust_clip, always_adapt, (on only) {list(self.ON_ONLY)} and (off only) {list(self.OFF_ONLY)}")
+            elif not any(value is off for off in self.OFF_ONLY[key]):
+                raise ValueError(f"FusedLamb: {key}={value!r} is not supported; only {key}={self.OFF_ONLY[key][0]!r} (the plain "
+                                 "update of timm.optim.Lamb) is")
+        for key, value in (("trust_clip", trust_clip), ("always_adapt", always_adapt)):
+            if not isinstance(value, bool):
+                raise ValueError(f"FusedLamb: {key}={value!r}: True or False is expected")
+        if max_grad_norm is not None and (isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float))
+                                          or not math.isfinite(max_grad_norm) or max_grad_norm <= 0):
+            raise ValueError(f"FusedLamb: max_grad_norm={max_grad_norm!r}: a positive float, or None for no built-in clip, is "
+                             "expected")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.trust_clip, self.always_adapt = trust_clip, always_adapt
+        super().__init__(params, lr, betas, eps, weight_decay)
+        # the tensor tables, over the trainable parameters only: a locked parameter's slots belong to no tensor
+        st = self.store
+        names = st.trainable_names()
+        group_of = {n: gi for gi, g in enumerate(self.param_groups) for n in g.get("param_names", ())}
+        slot_tensor = torch.full((st.total // 64,), -1, dtype=torch.int32)
+        tensor_slots = torch.zeros((len(names), 2), dtype=torch.int32)
+        for ti, n in enumerate(names):
+            sp = st.by_name[n]
+            lo = sp.offset // 64
+            hi = lo + (max(sp.numel, 1) + 63) // 64
+            slot_tensor[lo:hi] = ti
+            tensor_slots[ti, 0], tensor_slots[ti, 1] = lo, hi
+        self.tensor_names = names
+        self.tensor_group = torch.tensor([group_of.get(n, 0) for n in names], dtype=torch.int32)       # host: _fill_group_hyper
+        dev = st.device
+        self.slot_tensor, self.tensor_slots = slot_tensor.to(dev), tensor_slots.to(dev)
+        self.slot_sums = torch.zeros(2 * (st.total // 64), dtype=torch.float32, device=dev)     # {sum p^2, sum u^2} per slot
+        self.trust = torch.ones(len(names), dtype=torch.float32, device=dev)                    # r of the last step, per tensor
+        if self.group_hyper is None:        # one group: the same table and staging ring as with many (_init_groups)
+            n = self._group_hyper_floats(1)
+            cuda = torch.device(dev).type == "cuda"
+            self.group_hyper = torch.zeros(n, dtype=torch.float32, device=dev)
+            self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=dev)
+            for _ in range(4):
+                host = torch.zeros(n, dtype=torch.float32)
+                self._group_stage.append([host.pin_memory() if cuda else host, None])
+
+    def _uses_table(self) -> bool:
+        return True
+
+    def _clip_threshold(self, max_norm):
+        given = [float(x) for x in (max_norm, self.max_grad_norm) if x is not None and x > 0]
+        return min(given) if given else None
+
+    def _group_hyper_floats(self, n_groups: int) -> int:
+        return 2 + 2 * len(self.store.trainable_names())
+
+    def _fill_group_hyper(self, host: torch.Tensor) -> None:
+        g0 = self.param_groups[0]
+        ops.lamb_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
+                            self.tensor_group, g0["betas"][0], g0["betas"][1], self.step_count, host)
+
+    def _before_pieces(self, grad_scale, clip, table) -> None:
+        st, g = self.store, self.param_groups[0]
+        table = self.group_hyper if table is None else table
+        n_tensors = len(self.tensor_names)
+        for k, (lo, hi) in enumerate(self.ranges):
+            m, v = self._moments(k, lo, hi)
+            ops.lamb_moments(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.slot_tensor[lo // 64:], table, n_tensors,
+                             g["betas"][0], g["betas"][1], g["eps"], grad_scale, clip, self.slot_sums[2 * (lo // 64):])
+        ops.lamb_trust(self.slot_sums, st.total // 64, self.tensor_slots, table, n_tensors, self.always_adapt, self.trust_clip,
+                       self.trust)
+
+    def _update_groups(self, lo, hi, moments, grad_scale, clip, table) -> None:
+        st = self.store
+        m, v = moments
+        ops.lamb_apply(st.master[lo:hi], m, v, hi - lo, self.slot_tensor[lo // 64:], table, self.trust, len(self.tensor_names),
+                       self.param_groups[0]["eps"], st.master_bf16[lo:hi])
 
 
 def slot_table(store, group_names: Sequence[Sequence[str]]) -> torch.Tensor:
