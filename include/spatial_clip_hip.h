@@ -576,6 +576,26 @@ int sc_grad_norm_final(const double* partial, int n_partial, float grad_scale, f
  * take 16-byte loads and stores).  n == 0 launches nothing (and writes no partials) and returns 0; another mode, a NULL
  * grads, a NULL acc in modes 0 / 1, or partials in modes 0 / 1 are errors and launch nothing. */
 int sc_grad_accumulate(float* acc, float* grads, long long n, float scale, int mode, double* partial1024, void* stream);
+/* Weight averaging: an averaged copy `avg` of the master weights in the same flat fp32 layout, updated after an optimiser
+ * step (Lightning's EMAWeightAveraging / WeightAveraging callbacks over swa_utils.AveragedModel), 12 bytes per parameter:
+ *   SC_WAVG_SKIP  nothing is launched (sc_weight_average) / every thread returns before touching memory (the _dev form)
+ *   SC_WAVG_COPY  avg[i] = params[i]                              the first update (n_averaged == 0)
+ *   SC_WAVG_EMA   avg[i] = a * avg[i] + b * params[i]             a = decay, b = 1 - decay formed in double, rounded to fp32 once
+ *   SC_WAVG_MEAN  avg[i] = avg[i] + (params[i] - avg[i]) / a      a = n_averaged + 1; IEEE division
+ * Every product, sum, difference and quotient is rounded to fp32 on its own, never fused: the bits
+ * swa_utils.get_ema_avg_fn(decay) and AveragedModel's default rule give on a CPU.  sc_weight_average_dev runs the
+ * same body with {int op, float a, float b} read from 12 bytes of device memory `ctl`, so that a captured hipGraph replays an
+ * identical launch and the host rewrites the block in front of each replay; it gives the bits of sc_weight_average.
+ * sc_swap_f32 exchanges two buffers in place (validation on the average).  All pointers: any 4-byte aligned device pointers,
+ * the two buffers of a call not overlapping (16-byte aligned pairs take 16-byte loads and stores).  No atomics.  n == 0
+ * launches nothing and returns 0; an unknown op, a NULL pointer, a misaligned pointer or overlapping buffers are errors and
+ * launch nothing.  sc_weight_average_pass_floats: the floats one trip of the full grid covers (the launch constants of the
+ * three kernels: blocks x threads x 4); a longer buffer is grid-strided. */
+enum { SC_WAVG_SKIP = 0, SC_WAVG_COPY = 1, SC_WAVG_EMA = 2, SC_WAVG_MEAN = 3 };
+int sc_weight_average(float* avg, const float* params, long long n, int op, float a, float b, void* stream);
+int sc_weight_average_dev(float* avg, const float* params, long long n, const int* ctl, void* stream);
+int sc_swap_f32(float* a, float* b, long long n, void* stream);
+long long sc_weight_average_pass_floats(void);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,8 @@ What makes the launches identical from step to step:
   * the learning rate of the LambdaLR schedule and Adam's bias corrections are read by the AdamW kernel from a device triple
     the host refreshes before each replay (``FusedAdamW.refresh_hyper`` / ``sc_adamw_step_dev``); the clip coefficient was
     device-side already;
+  * with weight averaging (``optim.WeightAverager``) the update behind the optimiser's is captured in the form that reads
+    {op, a, b} -- skip, copy, EMA or mean and its scalars -- from a device block, refreshed with the optimiser's scalars;
   * R@k hit counters and the loss are device tensors; the host-side row counter is advanced by the wrapper.
 Same kernels on the same values in the same order: weights are BIT-IDENTICAL to the eager step's
 (tests/test_gpu_graph.py).  Not captured: multi-rank steps (RCCL collectives stay eager), the e4m3 path (its amax-history slot

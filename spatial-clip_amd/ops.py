@@ -799,6 +799,77 @@ def grad_accumulate(acc, grads, n, scale, mode, partial=None):
           "sc_grad_accumulate")
 
 
+WAVG_SKIP, WAVG_COPY, WAVG_EMA, WAVG_MEAN = range(4)
+
+
+def _wavg_pair(what: str, x, y, n: int, names) -> None:
+    for t, name in ((x, names[0]), (y, names[1])):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name}: expected torch.float32, got {t.dtype}")
+        if not t.is_contiguous() or n < 0 or t.numel() < n:
+            raise ValueError(f"{what}: {name} must be contiguous and hold n = {n} floats")
+    if x.device != y.device:
+        raise ValueError(f"{what}: {names[0]} and {names[1]} live on different devices")
+
+
+def weight_average(avg, params, n, op, a=0.0, b=0.0):
+    """One update of the averaged weights (``sc_weight_average``): ``WAVG_COPY`` ``avg = params``, ``WAVG_EMA``
+    ``avg = a * avg + b * params`` (a = decay, b = 1 - decay), ``WAVG_MEAN`` ``avg = avg + (params - avg) / a``
+    (a = n_averaged + 1), ``WAVG_SKIP`` nothing.  Every operation is rounded to fp32 on its own.  Host tensors evaluate the same
+    expressions with torch (tests of the schedule and the checkpoint layout; not a product path)."""
+    n, op = int(n), int(op)
+    if op not in (WAVG_SKIP, WAVG_COPY, WAVG_EMA, WAVG_MEAN):
+        raise ValueError(f"weight_average: op {op!r}: WAVG_SKIP, WAVG_COPY, WAVG_EMA or WAVG_MEAN")
+    _wavg_pair("weight_average", avg, params, n, ("avg", "params"))
+    if not avg.is_cuda:
+        if op == WAVG_SKIP or n == 0:
+            return
+        v, p = avg.view(-1)[:n], params.view(-1)[:n]
+        if op == WAVG_COPY:
+            v.copy_(p)
+        elif op == WAVG_EMA:
+            a32, b32 = torch.tensor(float(a), dtype=torch.float32), torch.tensor(float(b), dtype=torch.float32)
+            v.copy_(a32 * v + b32 * p)
+        else:
+            v.copy_(v + (p - v) / torch.tensor(float(a), dtype=torch.float32))
+        return
+    check(_lib.lib().sc_weight_average(avg.data_ptr(), params.data_ptr(), n, op, float(a), float(b), _stream()),
+          "sc_weight_average")
+
+
+def weight_average_dev(avg, params, n, ctl):
+    """The same update with ``{int32 op, float32 a, float32 b}`` read from the device block ``ctl`` (3 x 4 bytes; an int32
+    tensor whose second and third word hold the floats' bits): the launch a captured graph replays.  ``op == WAVG_SKIP``
+    touches nothing."""
+    n = int(n)
+    _wavg_pair("weight_average_dev", avg, params, n, ("avg", "params"))
+    _req(avg, torch.float32, "avg")
+    if ctl.dtype != torch.int32 or ctl.numel() < 3 or not ctl.is_contiguous() or ctl.device != avg.device:
+        raise ValueError("weight_average_dev: ctl must be 3 contiguous int32 on the device of avg")
+    check(_lib.lib().sc_weight_average_dev(avg.data_ptr(), params.data_ptr(), n, ctl.data_ptr(), _stream()),
+          "sc_weight_average_dev")
+
+
+def swap_f32(a, b, n):
+    """Exchange ``a[:n]`` and ``b[:n]`` in place (``sc_swap_f32``); overlapping buffers are refused.  Host tensors: with torch."""
+    n = int(n)
+    _wavg_pair("swap_f32", a, b, n, ("a", "b"))
+    if not a.is_cuda:
+        x, y = a.view(-1)[:n], b.view(-1)[:n]
+        if n and x.data_ptr() < y.data_ptr() + 4 * n and y.data_ptr() < x.data_ptr() + 4 * n:
+            raise ValueError("swap_f32: a and b must not overlap")
+        t = x.clone()
+        x.copy_(y)
+        y.copy_(t)
+        return
+    check(_lib.lib().sc_swap_f32(a.data_ptr(), b.data_ptr(), n, _stream()), "sc_swap_f32")
+
+
+def weight_average_pass_floats() -> int:
+    """Floats that one trip of the full grid of the weight-averaging kernels covers (their launch constants)."""
+    return int(_lib.lib().sc_weight_average_pass_floats())
+
+
 def adamw_step(p, g, m, v, n, lr, beta1, beta2, eps, wd, step, grad_scale, norm_clip, p_bf16=None):
     check(_lib.lib().sc_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(lr), float(beta1),
                                    float(beta2), float(eps), float(wd), int(step), float(grad_scale), _ptr(norm_clip),

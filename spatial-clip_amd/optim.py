@@ -10,6 +10,8 @@ launches ``ops.adamw_step_groups``, one streaming launch per range with a per-sl
 ``FusedLion(params, lr, betas, weight_decay)`` takes the kwargs of ``lion_pytorch.Lion`` / ``timm.optim.Lion`` and runs the
 same step forms with one moment (``ops.lion_step*``); ``FusedLamb`` takes the kwargs of ``timm.optim.Lamb``
 and runs them with per-tensor trust ratios (``ops.lamb_*``, section 4m); all three are ``_FlatOptimizer`` with their own launches.
+``WeightAverager`` keeps an averaged copy of the weights (Lightning's ``EMAWeightAveraging`` / ``WeightAveraging``) in a flat
+buffer of its own, updated behind every piece of those step forms (``ops.weight_average*``, section 4n).
 ``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
 (configs/scheduler/cosine.yaml): the first optimiser step runs with lr = 0."""
 from __future__ import annotations
@@ -78,6 +80,7 @@ class _FlatOptimizer:
         # graph-captured steps (graph.GraphedTrainStep): the step-dependent scalars live in device memory
         self.hyper = None           # fp32, what _refresh_scalar_hyper writes (AdamW: {lr, 1 - beta1^step, sqrt(1 - beta2^step)})
         self._hyper_host = None     # pinned staging of the same
+        self.averager: Optional["WeightAverager"] = None    # WeightAverager.attach: an averaged copy of the weights
 
     def _alloc_state(self, n: int) -> None:
         for name in self.STATE:
@@ -330,6 +333,9 @@ class _FlatOptimizer:
         from . import streams
         st = self.store
         st.wait_all()               # a step without a forward in between: the previous update must be complete
+        wa = self.averager
+        if wa is not None:
+            wa.begin_step(self.step_count - 1)
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
         buckets, order, copies, plans, owner = self._behind_plan(int(os.environ.get("SC_ADAMW_BUCKET", 16 * 1024 * 1024)))
         cur = torch.cuda.current_stream(st.device)
@@ -346,6 +352,8 @@ class _FlatOptimizer:
             for k in order:
                 lo, hi = buckets[k]
                 self._update_piece(owner[k], lo, hi, grad_scale, clip, table)
+                if wa is not None:          # on this stream, in front of the bucket's event: store.wait_all() covers it
+                    wa.after_piece(lo, hi)
                 st.refresh_range(lo, hi, copies[k], plans[k], fresh=(lo, hi))
                 done = torch.cuda.Event()
                 done.record(side)
@@ -357,6 +365,8 @@ class _FlatOptimizer:
         """Write {lr, 1 - beta1^step, sqrt(1 - beta2^step)} for the step about to run (``step_count`` already advanced) into
         the device triple ``self.hyper``: one 12-byte async H2D copy on the current stream, enqueued in front of the graph
         replay that reads it.  With two or more parameter groups: the group table ``self.group_hyper`` instead."""
+        if self.averager is not None:
+            self.averager.refresh_ctl(self.step_count - 1)
         if self._uses_table():
             self._refresh_group_hyper()
             return
@@ -374,6 +384,8 @@ class _FlatOptimizer:
         self._before_pieces(grad_scale, clip, None)
         for k, (lo, hi) in enumerate(self.ranges):
             self._update_piece(k, lo, hi, grad_scale, clip, dev=True)
+            if self.averager is not None:
+                self.averager.after_piece_captured(lo, hi)
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -397,12 +409,17 @@ class _FlatOptimizer:
         behind = os.environ.get("SC_ADAMW_BEHIND", "auto")
         if st.master.is_cuda and (behind == "1" or (behind not in ("0", "1") and st.total <= 200_000_000)):
             return self._step_behind_forward(grad_scale, max_norm, sumsq_partial)
+        wa = self.averager
+        if wa is not None:
+            wa.begin_step(self.step_count - 1)
         clip = self._clip(grad_scale, max_norm, sumsq_partial)
         if self._uses_table():
             self._refresh_group_hyper()
         self._before_pieces(grad_scale, clip, None)
         for k, (lo, hi) in enumerate(self.ranges):
             self._update_piece(k, lo, hi, grad_scale, clip)
+            if wa is not None:
+                wa.after_piece(lo, hi)
         st.refresh_compute_copies(mirror_is_fresh=True)
         return self.norm_clip
 
@@ -792,6 +809,245 @@ def build_param_groups(net, cfg, lr: float, weight_decay: Optional[float] = None
     if cfg.get("lr_scale"):
         groups = scaled_lr_groups(groups, lr, cfg["lr_scale"])
     return groups
+
+
+WEIGHT_AVERAGING_KINDS = ("ema", "mean")
+WEIGHT_AVERAGING_KEYS = ("decay", "update_every_n_steps", "update_starting_at_step", "update_starting_at_epoch", "device", "kind")
+
+
+def validate_weight_averaging(decay=0.999, update_every_n_steps=1, update_starting_at_step=None, update_starting_at_epoch=None,
+                              device=None, kind="ema") -> Dict[str, Any]:
+    """The arguments of ``lightning.pytorch.callbacks.EMAWeightAveraging`` as this build takes them, plus ``kind`` ("ema", or
+    "mean": ``AveragedModel``'s default equal average).  Returns the arguments of ``WeightAverager``; ValueError names the
+    argument that is refused."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if kind not in WEIGHT_AVERAGING_KINDS:
+        raise ValueError(f"weight_averaging: kind={kind!r}: one of {list(WEIGHT_AVERAGING_KINDS)} is expected")
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:
+        raise ValueError(f"weight_averaging: decay={decay!r}: a number in [0, 1] is expected")
+    if not is_int(update_every_n_steps) or update_every_n_steps < 1:
+        raise ValueError(f"weight_averaging: update_every_n_steps={update_every_n_steps!r}: an integer >= 1 is expected")
+    if update_starting_at_step is not None and (not is_int(update_starting_at_step) or update_starting_at_step < 0):
+        raise ValueError(f"weight_averaging: update_starting_at_step={update_starting_at_step!r}: None or an integer >= 0 is "
+                         "expected")
+    if update_starting_at_epoch is not None:
+        raise ValueError(f"weight_averaging: update_starting_at_epoch={update_starting_at_epoch!r} is not supported (updates "
+                         "are scheduled by optimiser step: update_starting_at_step); only None is accepted")
+    if device is not None:
+        raise ValueError(f"weight_averaging: device={device!r} is not supported (the average lives beside the master weights, "
+                         "on their device); only None is accepted")
+    return {"decay": float(decay), "update_every_n_steps": int(update_every_n_steps),
+            "update_starting_at_step": update_starting_at_step, "kind": kind}
+
+
+def check_weight_averaging_cfg(cfg) -> Optional[Dict[str, Any]]:
+    """``Trainer(callbacks={"weight_averaging": {...}})``: None (absent) or a mapping of ``validate_weight_averaging``'s
+    arguments."""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, Mapping):
+        raise ValueError(f"callbacks.weight_averaging={cfg!r}: a mapping with the keys {list(WEIGHT_AVERAGING_KEYS)} is expected")
+    unknown = [k for k in cfg if k not in WEIGHT_AVERAGING_KEYS]
+    if unknown:
+        raise ValueError(f"callbacks.weight_averaging: unknown key(s) {unknown}; accepted: {list(WEIGHT_AVERAGING_KEYS)}")
+    return validate_weight_averaging(**dict(cfg))
+
+
+class WeightAverager:
+    """An averaged copy of the weights (``lightning.pytorch.callbacks.EMAWeightAveraging`` / ``WeightAveraging`` over
+    ``torch.optim.swa_utils.AveragedModel``) for a net that has no ``nn.Module`` to copy: ``avg`` is a flat fp32 buffer in the
+    layout of ``store.master`` (4 more bytes per parameter) and one streaming kernel (``ops.weight_average``, 12 bytes per
+    parameter) updates it right behind the optimiser's update of every range or bucket, on the optimiser's stream.
+
+    After optimiser step ``s`` (0-based) an update happens iff ``s >= (update_starting_at_step or 0)`` and
+    ``s % update_every_n_steps == 0``; the first one copies the weights, every later one is ``decay * avg + (1 - decay) * p``
+    (``kind="ema"``) or ``avg + (p - avg) / (n_averaged + 1)`` (``kind="mean"``), with torch's CPU bits.  The trainable ranges are
+    averaged; locked ranges of ``avg`` are a copy of the masters made once.  The graph-captured step launches the form that
+    reads {op, a, b} from the device block ``ctl``, which ``refresh_ctl`` rewrites in front of every replay."""
+
+    def __init__(self, store, decay: float = 0.999, update_every_n_steps: int = 1, update_starting_at_step: Optional[int] = None,
+                 kind: str = "ema", update_starting_at_epoch=None, device=None):
+        args = validate_weight_averaging(decay, update_every_n_steps, update_starting_at_step, update_starting_at_epoch, device,
+                                         kind)
+        if getattr(store, "fp8", False):
+            raise ValueError("weight_averaging with precision='fp8' is not supported: the delayed e4m3 activation scales "
+                             "belong to the training weights, not to their average; use precision='bf16-mixed'")
+        self.store = store
+        self.decay, self.every, self.kind = args["decay"], args["update_every_n_steps"], args["kind"]
+        self.update_starting_at_step = args["update_starting_at_step"]
+        self.n_averaged = 0
+        self.latest_update_step = -1            # the optimiser step (0-based) of the last update; -1: none yet
+        self._decided: Optional[Tuple[int, int, float, float]] = None      # (step, op, a, b) of the step last decided
+        store.wait_all()
+        self.avg = store.master.clone()
+        self.ranges: List[Tuple[int, int]] = list(store.trainable_ranges())
+        self.ctl: Optional[torch.Tensor] = None        # device {int32 op, fp32 a, fp32 b, pad}: what the captured launches read
+        self._ctl_stage: list = []                      # pinned staging ring of the same: [host tensor, event of its copy]
+        self._ctl_next = 0
+
+    # ---- the schedule
+    def should_update(self, step: int) -> bool:
+        return step >= (self.update_starting_at_step or 0) and step % self.every == 0
+
+    def _decide(self, step: int) -> Tuple[int, float, float]:
+        """(op, a, b) of the update behind optimiser step ``step`` (0-based); counts it.  Asked again for the same step (the
+        capture of a graph refreshes the block of the step that then replays) it answers the same and counts nothing."""
+        step = int(step)
+        if self._decided is not None and self._decided[0] == step:
+            return self._decided[1:]
+        if not self.should_update(step):
+            out = (ops.WAVG_SKIP, 0.0, 0.0)
+        else:
+            if self.n_averaged == 0:
+                out = (ops.WAVG_COPY, 0.0, 0.0)
+            elif self.kind == "ema":
+                out = (ops.WAVG_EMA, self.decay, 1.0 - self.decay)      # 1 - decay in double; rounded to fp32 once, at the launch
+            else:
+                out = (ops.WAVG_MEAN, float(self.n_averaged + 1), 0.0)
+            self.n_averaged += 1
+            self.latest_update_step = step
+        self._decided = (step,) + out
+        return out
+
+    def attach(self, optimizer) -> "WeightAverager":
+        """Make ``optimizer`` (a ``_FlatOptimizer`` over the same store) call this averager behind every piece of its update.
+        Call after ``optimizer.attach_exchange`` and before a checkpoint is loaded."""
+        if getattr(optimizer, "store", None) is not self.store:
+            raise ValueError("WeightAverager.attach: the optimiser updates another ParamStore")
+        if getattr(optimizer, "exchange", None) is not None:
+            raise ValueError("weight_averaging with the sharded gradient exchange (SC_GRAD_EXCHANGE=sharded) is not supported: "
+                             "a rank updates 1/W of every bucket and gathers the rest behind the next forward; use the "
+                             "all-reduce exchange")
+        self.ranges = list(optimizer.ranges)
+        optimizer.averager = self
+        return self
+
+    # ---- the launches, called by the optimiser
+    def begin_step(self, step: int) -> None:
+        """The eager step forms: decide the update of optimiser step ``step`` before its pieces run."""
+        self._decide(step)
+
+    def after_piece(self, lo: int, hi: int) -> None:
+        """Behind the optimiser's update of flat[lo:hi] (a trainable range or a bucket of one), on the current stream."""
+        op, a, b = self._decided[1:]
+        if op != ops.WAVG_SKIP:
+            ops.weight_average(self.avg[lo:hi], self.store.master[lo:hi], hi - lo, op, a, b)
+
+    def after_piece_captured(self, lo: int, hi: int) -> None:
+        """The same inside a graph capture: {op, a, b} are read from ``ctl`` by every replay."""
+        ops.weight_average_dev(self.avg[lo:hi], self.store.master[lo:hi], hi - lo, self._ctl())
+
+    def _ctl(self) -> torch.Tensor:
+        if self.ctl is None:
+            dev = self.store.device
+            cuda = torch.device(dev).type == "cuda"
+            self.ctl = torch.zeros(4, dtype=torch.int32, device=dev)
+            for _ in range(4):
+                host = torch.zeros(4, dtype=torch.int32)
+                self._ctl_stage.append([host.pin_memory() if cuda else host, None])
+        return self.ctl
+
+    def refresh_ctl(self, step: int) -> None:
+        """Write {op, a, b} of optimiser step ``step`` into ``ctl``: one 16-byte async copy on the current stream, in front of
+        the replay that reads it.  The pinned staging is a ring of four, each with the event of its last copy (as the
+        optimiser's group table, ``_refresh_group_hyper``): a host running ahead of the device never rewrites a block that a
+        pending copy still has to read."""
+        import struct
+        op, a, b = self._decide(step)
+        ctl = self._ctl()
+        slot = self._ctl_stage[self._ctl_next]
+        self._ctl_next = (self._ctl_next + 1) % len(self._ctl_stage)
+        if slot[1] is not None:
+            slot[1].synchronize()
+        bits = struct.unpack("<2i", struct.pack("<2f", a, b))      # rounded to fp32 as the host-scalar launch rounds them
+        slot[0][0], slot[0][1], slot[0][2] = int(op), bits[0], bits[1]
+        ctl.copy_(slot[0], non_blocking=True)
+        if ctl.is_cuda:
+            slot[1] = torch.cuda.Event()
+            slot[1].record(torch.cuda.current_stream(ctl.device))
+
+    # ---- validation and the end of training
+    def swap(self) -> None:
+        """Exchange masters and average in place and refresh every compute copy."""
+        st = self.store
+        st.wait_all()
+        ops.swap_f32(st.master, self.avg, st.total)
+        self._refresh_copies()
+
+    def _refresh_copies(self) -> None:
+        if self.store.master.is_cuda:       # (a host-side store -- tests of the layout -- has no compute copies to refresh)
+            self.store.refresh_compute_copies()
+
+    def applied(self):
+        """Context manager: the net computes with the averaged weights inside (masters and average exchanged in place, compute
+        copies refreshed) and with the training weights, bit for bit, afterwards."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            self.swap()
+            try:
+                yield self
+            finally:
+                self.swap()
+        return ctx()
+
+    def copy_to_model(self) -> None:
+        """The end of training (Lightning's ``on_train_end``): the model holds the average.  The training weights stay in
+        checkpoints written before (``current_model_state``)."""
+        st = self.store
+        st.wait_all()
+        st.master.copy_(self.avg)
+        self._refresh_copies()
+
+    def reset_from_model(self) -> None:
+        """Start over from the model's weights (a checkpoint without an average was loaded): ``n_averaged = 0``."""
+        self.store.wait_all()
+        self.avg.copy_(self.store.master)
+        self.n_averaged, self.latest_update_step, self._decided = 0, -1, None
+
+    # ---- checkpoints
+    def _named(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return {s.name: flat[s.offset:s.offset + s.numel].view(s.shape).detach().clone() for s in self.store.specs}
+
+    def averaged_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The average under the names of ``net.state_dict()``; the model's weights while nothing has been averaged."""
+        self.store.wait_all()
+        return self._named(self.avg if self.n_averaged > 0 else self.store.master)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """The ``"weight_averaging"`` entry of a checkpoint, whose ``"state_dict"`` carries ``averaged_state_dict()``."""
+        self.store.wait_all()
+        return {"current_model_state": self._named(self.store.master), "n_averaged": int(self.n_averaged),
+                "latest_update_step": int(self.latest_update_step), "kind": self.kind, "decay": float(self.decay)}
+
+    def load_state_dict(self, sd: Mapping, averaged: Optional[Mapping] = None) -> None:
+        """``sd``: a checkpoint's ``"weight_averaging"`` entry; ``averaged``: its ``"state_dict"`` (None: the masters hold it, as
+        after ``net.load_checkpoint_state_dict``).  The average takes ``averaged``, the masters ``current_model_state``."""
+        missing = [k for k in ("current_model_state", "n_averaged", "latest_update_step", "kind", "decay") if k not in sd]
+        if missing:
+            raise ValueError(f"WeightAverager.load_state_dict: the entry lacks {missing}")
+        if sd["kind"] != self.kind:
+            raise ValueError(f"WeightAverager.load_state_dict: the file's average is of kind {sd['kind']!r}, this averager's "
+                             f"kind={self.kind!r}")
+        st = self.store
+        st.wait_all()
+        if averaged is None:
+            self.avg.copy_(st.master)
+        else:
+            for s in st.specs:
+                self.avg[s.offset:s.offset + s.numel].view(s.shape).copy_(averaged[s.name].to(self.avg.device, torch.float32))
+        current = sd["current_model_state"]
+        lacking = [s.name for s in st.specs if s.name not in current]
+        if lacking:
+            raise ValueError(f"WeightAverager.load_state_dict: current_model_state lacks {lacking[:5]} ({len(lacking)} in all)")
+        with torch.no_grad():
+            for s in st.specs:
+                st.master[s.offset:s.offset + s.numel].view(s.shape).copy_(current[s.name].to(st.master.device, torch.float32))
+        self._refresh_copies()
+        self.n_averaged, self.latest_update_step = int(sd["n_averaged"]), int(sd["latest_update_step"])
+        self._decided = None
 
 
 class GradAccumulator:

@@ -14,7 +14,9 @@ after every N-th batch and after the epoch's last one, on the sum of the group's
 (``optim.GradAccumulator``; DESIGN.md "Gradient accumulation").  Checkpoints (reference: ModelCheckpoint monitor ``val/R@1``,
 ``save_last``; configs/callbacks/default.yaml:8-14, gated by ``save_ckpt`` -> ``enable_checkpointing``,
 src/train.py:77-99) are written by rank 0 under ``default_root_dir/checkpoints``; ``fit(ckpt_path=...)`` resumes
-weights, optimiser moments, LR schedule and the step counter (src/train.py:119)."""
+weights, optimiser moments, LR schedule and the step counter (src/train.py:119).  ``callbacks["weight_averaging"]`` (the
+arguments of Lightning's ``EMAWeightAveraging``) keeps an averaged copy of the weights on the device (``optim.WeightAverager``;
+DESIGN.md "Weight averaging"): validation, the checkpoints' ``state_dict`` and the model after ``fit`` are the average."""
 from __future__ import annotations
 
 import os
@@ -24,7 +26,7 @@ from typing import Any, Dict, List, Optional
 import torch
 
 from . import comm, graph, streams
-from .optim import GradAccumulator, validate_accumulate_grad_batches
+from .optim import GradAccumulator, WeightAverager, check_weight_averaging_cfg, validate_accumulate_grad_batches
 
 
 def _to_device(batch: Dict[str, Any], device) -> Dict[str, Any]:
@@ -155,8 +157,28 @@ class Trainer:
                                    "patience": int(es.get("patience", 3)), "min_delta": float(es.get("min_delta", 0.0)),
                                    "best": None, "wait": 0}
         self.should_stop = False
+        # weight_averaging {decay, update_every_n_steps, update_starting_at_step, kind}: what Lightning's EMAWeightAveraging /
+        # WeightAveraging callback takes (configs/callbacks/ema.yaml); the averager itself is built by fit()
+        self.weight_averaging = check_weight_averaging_cfg(cbs.get("weight_averaging"))
+        self.weight_averager: Optional[WeightAverager] = None
+        if self.weight_averaging is not None:
+            if self.precision == "fp8":
+                raise ValueError(f"callbacks.weight_averaging with precision={precision!r}: not supported (the delayed e4m3 "
+                                 "activation scales belong to the training weights, not to their average); use 'bf16-mixed'")
+            if comm.grad_exchange_mode() == "sharded":
+                raise ValueError("callbacks.weight_averaging with SC_GRAD_EXCHANGE=sharded: not supported (a rank updates 1/W of "
+                                 "every bucket); use SC_GRAD_EXCHANGE=allreduce (the default)")
 
     def _validate(self, model, datamodule) -> Dict[str, float]:
+        """Validation on the averaged weights once an average exists (``callbacks["weight_averaging"]``; Lightning's
+        WeightAveraging swaps them in the same way), else on the model's own."""
+        wa = self.weight_averager
+        if wa is None or wa.n_averaged == 0:
+            return self._validate_pass(model, datamodule)
+        with wa.applied():
+            return self._validate_pass(model, datamodule)
+
+    def _validate_pass(self, model, datamodule) -> Dict[str, float]:
         """One pass over the validation loader: val/loss, the module's retrieval metrics, the zero-shot metric if a
         gene bank is configured (src/models/spatial_clip_module.py:104-136)."""
         val = datamodule.val_dataloader()
@@ -218,6 +240,14 @@ class Trainer:
         model.net.grad_bucket_hook = reducer.bucket_ready if reducer is not None else None
         if hasattr(opt, "attach_exchange"):
             opt.attach_exchange(reducer)
+        # the averaged weights: behind attach_exchange (the sharded optimiser is refused), in front of the checkpoint (which
+        # may carry an average)
+        self.weight_averager = None
+        if self.weight_averaging is not None:
+            if not hasattr(opt, "averager"):
+                raise ValueError(f"callbacks.weight_averaging needs one of this package's fused optimisers; got "
+                                 f"{type(opt).__name__}")
+            self.weight_averager = WeightAverager(model.net.store, **self.weight_averaging).attach(opt)
         if ckpt_path:
             if not os.path.isfile(ckpt_path):
                 raise FileNotFoundError(f"ckpt_path {ckpt_path!r} does not exist")
@@ -312,6 +342,8 @@ class Trainer:
                 break
         self.callback_metrics = {k: v for k, v in self.history[-1].items() if isinstance(v, float)} if self.history else {}
         model.net.store.wait_all()      # the last optimiser update may run behind the (absent) next forward: fit returns finished weights
+        if self.weight_averager is not None and self.weight_averager.n_averaged > 0:
+            self.weight_averager.copy_to_model()        # Lightning's on_train_end: the model holds the average
 
     def _val_in_epoch(self, model, datamodule, val_every: int, i: int, n_train: int, epoch: int) -> None:
         """val_check_interval inside an epoch: counts TRAINING BATCHES, also under accumulate_grad_batches (as Lightning)."""
@@ -377,7 +409,9 @@ class Trainer:
         """``state_dict`` uses the reference ``CLIP.state_dict()`` key names, so the file loads into open_clip too.
         ``optimizer_state``: what ``optimizer.state_dict()`` returned on THIS rank (with the sharded optimiser that call is a
         collective, so a caller that writes on one rank only passes the result in)."""
-        ck = {"state_dict": {k: v.cpu() for k, v in model.net.state_dict().items()}, "global_step": global_step}
+        wa = getattr(optimizer, "averager", None)
+        weights = model.net.state_dict() if wa is None else wa.averaged_state_dict()     # what validation ran on
+        ck = {"state_dict": {k: v.cpu() for k, v in weights.items()}, "global_step": global_step}
         if optimizer is not None:
             osd = optimizer_state if optimizer_state is not None else optimizer.state_dict()
             ck["optimizer"] = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in osd.items()}
@@ -388,6 +422,10 @@ class Trainer:
             ck["fp8_scaling"] = fp8         # delayed e4m3 scales + amax history: a resumed run continues with them
         if getattr(model.net, "patch_dropout", 0.0) > 0.0:
             ck["patch_dropout_draw"] = int(model.net.patch_dropout_draw)      # a resumed run draws the subsets the run would have
+        if wa is not None:      # the training weights beside the average, and the averager's counters
+            entry = wa.state_dict()
+            entry["current_model_state"] = {k: v.cpu() for k, v in entry["current_model_state"].items()}
+            ck["weight_averaging"] = entry
         torch.save(ck, path)
 
     @staticmethod
@@ -396,6 +434,17 @@ class Trainer:
         ``net.model.``, ``module.`` are stripped: net.strip_checkpoint_prefix)."""
         ck = torch.load(path, map_location="cpu", weights_only=False)
         model.net.load_checkpoint_state_dict(ck, source=path)          # resets the fp8 scaling history ...
+        # Averaged weights: "state_dict" is the average and "weight_averaging" carries the training weights.  test / eval
+        # (no optimiser) read the average; fit trains on from the training weights, with or without an averager of its own.
+        wa = getattr(optimizer, "averager", None)
+        entry = ck.get("weight_averaging")
+        if wa is not None:
+            if isinstance(entry, dict):
+                wa.load_state_dict(entry)       # average <- the masters just loaded; masters <- current_model_state
+            else:
+                wa.reset_from_model()
+        elif optimizer is not None and isinstance(entry, dict):
+            model.net.load_state_dict(entry["current_model_state"])
         if hasattr(model.net, "load_fp8_scaling_state"):
             model.net.load_fp8_scaling_state(ck.get("fp8_scaling"))     # ... and restores it when the file carries one
         if "patch_dropout_draw" in ck and hasattr(model.net, "patch_dropout_draw"):
