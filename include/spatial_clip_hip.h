@@ -356,6 +356,21 @@ int sc_contrastive_loss_bwd(float* z_inout, int B, int G, const float* logit_sca
                             const float* grad_out, float* rowgrad, float* dscale, float* dbias, void* stream);
 /* RecallAtK (src/models/components/metrics.py:22-36) on the local [B,B] block of z[0]: hits3 += {R@1,R@5,R@10}. */
 int sc_recall_hits(const float* z_image_rows, int G, int B, int col0, int* hits3, void* stream);
+/* Group cache of cached-feature gradient accumulation (Trainer accum_freq = N; open_clip --accum-freq): ONE launch copies what
+ * micro-batch j leaves for the group's loss into row block j -- rows [j*B, (j+1)*B) -- of the contiguous caches
+ * image_cache / text_cache [N*B][D] (fp32), image_id_cache / text_id_cache [N*B] (int64), neighbor_id_cache [N*B][K] (int64)
+ * and neighbor_alpha_cache [N*B][K] (fp32).  image_features / text_features [B][D] have row strides ld_image / ld_text >= D
+ * (in floats); the id vectors and neighbour matrices are contiguous.  Each of image_tile_ids, text_tile_ids,
+ * neighbor_tile_ids and neighbor_alphas may be NULL (ClipLoss, SigLipLoss): that cache is then not touched, and with K == 0
+ * neither neighbour cache is.  Plain loads and stores, 16 bytes wide where a source row and its destination row are both
+ * 16-byte aligned, 4 bytes wide otherwise and in a row's last partial 16 bytes; no atomics; nothing outside row block j is
+ * written.  Bad shapes (B, D, N <= 0, K < 0, j outside [0, N), a stride below D) return an error and launch nothing. */
+int sc_group_cache_put(const float* image_features, long long ld_image, const float* text_features, long long ld_text,
+                       const long long* image_tile_ids, const long long* text_tile_ids,
+                       const long long* neighbor_tile_ids, const float* neighbor_alphas, float* image_cache,
+                       float* text_cache, long long* image_id_cache, long long* text_id_cache,
+                       long long* neighbor_id_cache, float* neighbor_alpha_cache, int B, int D, int K, int j, int N,
+                       void* stream);
 /* SigLipLoss (src/open_clip/loss.py:330-460) on the device.  z_inout[B][G] = local image_features . all_text^T; the
  * positives are the diagonal of the rank's block (column col0 + i).  One pass: loss terms softplus(-y x) with
  * x = s z + b, dz = s (dl/dx) / B written over z; rowpart[B][3] = per-row {sum loss, sum (dl/dx) z, sum dl/dx}; a

@@ -630,6 +630,75 @@ extern "C" int sc_scale_by_scalar(const float* x, const float* s, float* out, lo
     return 0;
 }
 
+// Group cache of cached-feature gradient accumulation (Trainer accum_freq; open_clip --accum-freq): one launch copies what
+// micro-batch j of a group of N leaves for the group's loss -- features of both towers, tile ids, neighbour ids and alphas --
+// into row block j of the caches.  Everything is moved as 4-byte words, four at a time (one 16-byte load and store) where the
+// source and destination rows are both 16-byte aligned, word by word otherwise and in a row's last partial quad.
+struct CachePutSeg {
+    const unsigned* src; unsigned* dst;         // dst already points at row block j
+    long long src_pitch, dst_pitch;             // in words
+    int rows, words;                            // words per row
+};
+struct CachePutArgs { CachePutSeg seg[6]; };
+
+__global__ void group_cache_put_kernel(CachePutArgs a) {
+    const CachePutSeg s = a.seg[blockIdx.y];
+    if (s.src == nullptr || s.rows <= 0 || s.words <= 0) return;
+    const long long qpr = ((long long)s.words + 3) / 4;          // quads per row, the last one possibly partial
+    const long long total = qpr * s.rows;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long long)gridDim.x * blockDim.x) {
+        const long long row = q / qpr;
+        const int c = (int)(q - row * qpr) * 4;
+        const unsigned* sp = s.src + row * s.src_pitch;
+        unsigned* dp = s.dst + row * s.dst_pitch;
+        const bool aligned = (((size_t)sp | (size_t)dp) & 15) == 0;
+        if (aligned && c + 4 <= s.words) {
+            *reinterpret_cast<uint4*>(dp + c) = *reinterpret_cast<const uint4*>(sp + c);
+        } else {
+            const int e = c + 4 <= s.words ? c + 4 : s.words;
+            for (int i = c; i < e; ++i) dp[i] = sp[i];
+        }
+    }
+}
+
+extern "C" int sc_group_cache_put(const float* image_features, long long ld_image, const float* text_features,
+                                  long long ld_text, const long long* image_tile_ids, const long long* text_tile_ids,
+                                  const long long* neighbor_tile_ids, const float* neighbor_alphas, float* image_cache,
+                                  float* text_cache, long long* image_id_cache, long long* text_id_cache,
+                                  long long* neighbor_id_cache, float* neighbor_alpha_cache, int B, int D, int K, int j,
+                                  int N, void* stream) {
+    SC_CHECK(B > 0 && D > 0 && K >= 0 && N > 0 && j >= 0 && j < N, "sc_group_cache_put: bad shape B=%d D=%d K=%d j=%d N=%d",
+             B, D, K, j, N);
+    SC_CHECK(ld_image >= D && ld_text >= D, "sc_group_cache_put: input row strides %lld / %lld below D=%d", ld_image, ld_text, D);
+    SC_CHECK(image_features != nullptr && text_features != nullptr && image_cache != nullptr && text_cache != nullptr,
+             "sc_group_cache_put: null feature argument");
+    SC_CHECK((image_tile_ids == nullptr || image_id_cache != nullptr) && (text_tile_ids == nullptr || text_id_cache != nullptr),
+             "sc_group_cache_put: tile ids given without their cache");
+    SC_CHECK(K == 0 || ((neighbor_tile_ids == nullptr || neighbor_id_cache != nullptr) &&
+                        (neighbor_alphas == nullptr || neighbor_alpha_cache != nullptr)),
+             "sc_group_cache_put: neighbours given without their cache");
+    const long long r0 = (long long)j * B;      // first row of block j
+    CachePutArgs a;
+    a.seg[0] = {(const unsigned*)image_features, (unsigned*)(image_cache + r0 * D), ld_image, D, B, D};
+    a.seg[1] = {(const unsigned*)text_features, (unsigned*)(text_cache + r0 * D), ld_text, D, B, D};
+    a.seg[2] = {(const unsigned*)image_tile_ids, (unsigned*)(image_tile_ids ? image_id_cache + r0 : nullptr), 0, 0, 1, 2 * B};
+    a.seg[3] = {(const unsigned*)text_tile_ids, (unsigned*)(text_tile_ids ? text_id_cache + r0 : nullptr), 0, 0, 1, 2 * B};
+    const bool nb = K > 0 && neighbor_tile_ids != nullptr, al = K > 0 && neighbor_alphas != nullptr;
+    a.seg[4] = {(const unsigned*)(nb ? neighbor_tile_ids : nullptr), (unsigned*)(nb ? neighbor_id_cache + r0 * K : nullptr),
+                2LL * K, 2LL * K, B, 2 * K};
+    a.seg[5] = {(const unsigned*)(al ? neighbor_alphas : nullptr), (unsigned*)(al ? neighbor_alpha_cache + r0 * K : nullptr),
+                K, K, B, K};
+    long long quads = (long long)B * ((D + 3) / 4);
+    const long long quads_nb = (long long)B * ((2 * K + 3) / 4), quads_id = (2LL * B + 3) / 4;
+    if (quads_nb > quads) quads = quads_nb;
+    if (quads_id > quads) quads = quads_id;
+    long long blocks = (quads + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    group_cache_put_kernel<<<dim3((unsigned)blocks, 6), 256, 0, (hipStream_t)stream>>>(a);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int sc_exp_scalar(const float* x, float* y, void* stream) {
     exp_scalar_kernel<<<1, 1, 0, (hipStream_t)stream>>>(x, y);
     SC_LAUNCH_CHECK();

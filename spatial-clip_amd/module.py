@@ -236,6 +236,135 @@ class SpatialClipLitModule(torch.nn.Module):
         self.log_dict(self.train_metrics, on_step=False, on_epoch=True, sync_dist=True)
         return output["loss"]
 
+    # ------------------------------------------------------------------ cached-feature gradient accumulation (accum_freq)
+    def check_cached_accumulation(self, accum_freq: int) -> None:
+        """What the cached-feature form cannot run with; ValueError naming the offending values."""
+        from . import losses
+        if self.dist_net is not None or isinstance(self.loss_fn, losses.DistillClipLoss):
+            raise ValueError(f"accum_freq={accum_freq} with {type(self.loss_fn).__name__} / dist_net: distillation has no "
+                             "cached-feature form here (the teacher's features would need a cache of their own); use accum_freq=1")
+        if not isinstance(self.loss_fn, (losses.ClipLoss, losses.SpatialLoss, losses.SigLipLoss)):
+            raise ValueError(f"accum_freq={accum_freq} with {type(self.loss_fn).__name__}: the group loss is evaluated by the "
+                             "fused head; ClipLoss, SpatialLoss and SigLipLoss are supported")
+        if getattr(self.net, "precision", "bf16") == "fp8":
+            raise ValueError(f"accum_freq={accum_freq} with precision='fp8': the caching pass would advance the delayed scaling")
+        if comm.is_dist():
+            raise ValueError(f"accum_freq={accum_freq} under a process group of {comm.world()[1]} ranks: the group cache is "
+                             "single-process")
+
+    def group_accumulator(self, accum_freq: int):
+        """The ``optim.GradAccumulator`` (scale 1: the group loss is already a mean over all N * B pairs) the group step folds with."""
+        from . import optim
+        acc = getattr(self, "_group_accum", None)
+        if acc is None or acc.every != accum_freq or acc.store is not self.net.store:
+            acc = self._group_accum = optim.GradAccumulator(self.net.store, accum_freq, scale=1.0)
+        return acc
+
+    def _group_cache(self, N: int, B: int, D: int, K: Optional[int]) -> Dict[str, Optional[torch.Tensor]]:
+        """The caches of one group shape, allocated once: features [N*B, D] of both towers and, for SpatialLoss (K is not None),
+        the tile ids [N*B] and the neighbour ids / alphas [N*B, K]."""
+        key = (N, B, D, K)
+        c = getattr(self, "_group_caches", None)
+        if c is None or c["key"] != key:
+            G, dev = N * B, self.device
+            c = {"key": key, "image": torch.empty((G, D), dtype=torch.float32, device=dev),
+                 "text": torch.empty((G, D), dtype=torch.float32, device=dev), "ids_i": None, "ids_t": None, "nb": None, "al": None}
+            if K is not None:
+                c.update(ids_i=torch.empty(G, dtype=torch.int64, device=dev), ids_t=torch.empty(G, dtype=torch.int64, device=dev),
+                         nb=torch.empty((G, K), dtype=torch.int64, device=dev),
+                         al=torch.empty((G, K), dtype=torch.float32, device=dev))
+            self._group_caches = c
+        return c
+
+    def cached_group_step(self, batches, partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimiser step's gradient from N micro-batches of B pairs as ONE batch of G = N * B (open_clip's ``--accum-freq``,
+        open_clip_train/train.py:113-192).  Phase 1: ``net.cache_features`` on every micro-batch (training
+        semantics, not differentiated), its features and SpatialLoss inputs copied into row block j of the group cache
+        (``sc_group_cache_put``).  The loss: the fused head once on the cache, as a single-process batch of G -- a neighbour id
+        found in another micro-batch's rows gets its weight.  Phase 2: each micro-batch forward again with the same patch
+        dropout draw, its backward seeded with rows [jB, (j+1)B) of the head's feature gradients (views); the first one also
+        takes d logit_scale / d logit_bias (ONCE per group: the exact gradient, where open_clip's loop applies it N times); each
+        gradient is folded at scale 1 (``group_accumulator``).  On return ``store.grad`` holds the gradient of the group loss,
+        ready for ``optimizer.step``; ``partial`` (``accumulator.sumsq_partial()``) collects the clip's sums of squares in the
+        last fold.  Returns the group loss (0-d, device); ``train/loss`` logs it and the train metrics see the G x G block once."""
+        from . import contrastive, losses, streams
+        batches = list(batches)                 # the group keeps its N input batches until phase 2 has used them
+        N = len(batches)
+        if N < 1:
+            raise ValueError("cached_group_step: an empty group")
+        self.check_cached_accumulation(N)
+        net, loss_fn = self.net, self.loss_fn
+        spatial = isinstance(loss_fn, losses.SpatialLoss)
+        siglip = isinstance(loss_fn, losses.SigLipLoss)
+        accum = self.group_accumulator(N)
+        self.net.feature_gather = None
+        with streams.chain_stream():
+            # ---- phase 1: features of every micro-batch, training semantics, nothing kept for a backward
+            draw0 = net.patch_dropout_draw
+            cache = None
+            for j, b in enumerate(batches):
+                img, txt = net.cache_features(b["images"], b["texts"], draw=draw0 + j)
+                B, D = img.shape
+                if cache is None:
+                    K = int(b["neighbor_tile_ids"].shape[1]) if spatial else None
+                    cache = self._group_cache(N, B, D, K)
+                    B0 = B
+                elif B != B0:
+                    raise ValueError(f"cached_group_step: micro-batch {j} has {B} pairs, the group's first one {B0}: every "
+                                     "micro-batch of a group must have the same size")
+                if spatial:
+                    ops.group_cache_put(img, txt, cache["image"], cache["text"], j, N,
+                                        image_tile_ids=b["image_tile_ids"].contiguous(), text_tile_ids=b["text_tile_ids"].contiguous(),
+                                        neighbor_tile_ids=b["neighbor_tile_ids"].contiguous(),
+                                        neighbor_alphas=b["neighbor_alphas"].contiguous().float(),
+                                        image_id_cache=cache["ids_i"], text_id_cache=cache["ids_t"],
+                                        neighbor_id_cache=cache["nb"], neighbor_alpha_cache=cache["al"])
+                else:
+                    ops.group_cache_put(img, txt, cache["image"], cache["text"], j, N)
+            # ---- the loss of the whole group, once, and its gradients with respect to the cached features
+            has_bias = net.has_logit_bias
+            net.store.wait_names(["logit_scale", "logit_bias"] if has_bias else ["logit_scale"])
+            scale = torch.empty(1, dtype=torch.float32, device=self.device)
+            ops.exp_scalar(net.store.p("logit_scale").view(1), scale)
+            bias = net.store.p("logit_bias").detach() if has_bias else None
+            metrics = self.train_metrics
+            metrics._ensure(self.device)
+            if siglip:
+                res = contrastive.siglip_forward_backward(cache["image"], cache["text"], scale, bias, recall_hits=metrics.hits,
+                                                          join_local=True)
+            else:
+                res = contrastive.contrastive_forward_backward(
+                    cache["image"], cache["text"], scale, mode=loss_fn.mode, image_tile_ids=cache["ids_i"],
+                    text_tile_ids=cache["ids_t"], neighbor_tile_ids=cache["nb"], neighbor_alphas=cache["al"],
+                    cap_logit_scale=loss_fn.cap_logit_scale, temp_reg_weight=loss_fn.temp_reg_weight,
+                    neighbor_alpha_scale=loss_fn.neighbor_alpha_scale, logit_bias=bias, recall_hits=metrics.hits,
+                    want_recall=False, join_local=True)
+            metrics.add_hits(N * B0)
+            loss_fn.last = res
+            loss = res["loss"]
+            # ---- phase 2: each micro-batch again, differentiated, seeded with its rows of the group's feature gradients
+            # (logit_scale / logit_bias: the group's gradient on the first micro-batch, a resident 0 on the others -- written by
+            # the same in-tree launches, where ``None`` would zero them with an ATen fill)
+            zero = getattr(self, "_zero1", None)
+            if zero is None or zero.device != self.device:
+                zero = self._zero1 = torch.zeros(1, dtype=torch.float32, device=self.device)
+            replay = net.patch_dropout > 0.0 and net.training
+            for j, b in enumerate(batches):
+                if replay:
+                    net.patch_dropout_draw = draw0 + j      # the draw of its caching pass: the same kept patches
+                with torch.enable_grad():
+                    net(b["images"], b["texts"])            # a training forward: the towers hold what this backward reads
+                rows = slice(j * B0, (j + 1) * B0)
+                net.store.wait_all()        # as _NetFn.backward: an update running behind the forward reads the gradients
+                net._backward(res["d_image"][rows], res["d_text"][rows], res["d_scale"] if j == 0 else zero,
+                              (res["d_bias"] if j == 0 else zero) if has_bias else None)
+                last = j == N - 1
+                accum.fold(j == 0, last, partial=partial if last else None)
+        self._loss_terms = {}
+        self.log("train/loss", loss, on_step=True, on_epoch=True, prog_bar=True, sync_dist=True)
+        self.log_dict(self.train_metrics, on_step=False, on_epoch=True, sync_dist=True)
+        return loss
+
     def on_validation_start(self) -> None:
         """Build the gene bank once: text-tower embeddings of every gene name in ``global_hvg_path``
         (spatial_clip_module.py:73-103).  ``net.tokenizer`` must turn a list of gene names into token ids; the

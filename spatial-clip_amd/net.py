@@ -530,6 +530,25 @@ class SpatialClipNet(torch.nn.Module):
         return {"image_features": img, "text_features": txt, "logit_scale": s,
                 "logit_bias": out[3] if len(out) > 3 else None}
 
+    def cache_features(self, images: torch.Tensor, texts: torch.Tensor, draw: Optional[int] = None):
+        """The caching pass of cached-feature gradient accumulation (``Trainer(accum_freq=N)``; open_clip's
+        ``--accum-freq``, open_clip_train/train.py:113-131): a forward with TRAINING semantics that will not be differentiated.
+        Patch dropout is armed with the given ``draw`` -- the differentiated forward that later replays this micro-batch with
+        ``patch_dropout_draw == draw`` keeps the same patches -- and ``patch_dropout_draw`` itself does not move; nothing is
+        recorded for the fp8 scaling, no ``FeatureGather`` prefetch is armed, no autograd node is made.  Returns
+        ``(image_features, text_features)``: the towers' L2-normalised fp32 [B, D] outputs, fresh tensors of this pass."""
+        if self.precision == "fp8":
+            raise ValueError("cache_features with precision='fp8': the delayed e4m3 scales of a training forward are not "
+                             "replayable; the cached-feature form runs on 'bf16'")
+        with torch.no_grad():
+            self._mark_pass(False)
+            if self.patch_dropout > 0.0 and self.training:
+                self.vision.drop = {"seed": self.seed, "draw": int(self.patch_dropout_draw if draw is None else draw),
+                                    "rank": comm.world()[0], "keep": None}
+            txt = self.second.forward(texts)
+            img = self.vision.forward(images)
+        return img, txt
+
     def _mark_pass(self, train_pass: bool) -> None:
         """Tell the stacks whether the forward about to run will be differentiated.  Only such a pass records e4m3 maxima,
         consumes the delayed scales or overwrites the per-block e4m3 copies the backward reads; evaluation forwards --

@@ -677,6 +677,45 @@ def recall_hits(z_img_rows, G, B, col0, hits3):
     check(_lib.lib().sc_recall_hits(z_img_rows.data_ptr(), G, B, col0, hits3.data_ptr(), _stream()), "sc_recall_hits")
 
 
+def group_cache_put(image_features, text_features, image_cache, text_cache, j: int, N: int, image_tile_ids=None,
+                    text_tile_ids=None, neighbor_tile_ids=None, neighbor_alphas=None, image_id_cache=None, text_id_cache=None,
+                    neighbor_id_cache=None, neighbor_alpha_cache=None) -> None:
+    """Row block ``j`` of the group caches of ``Trainer(accum_freq=N)`` <- one micro-batch (``sc_group_cache_put``, one
+    launch): ``image_features`` / ``text_features`` fp32 [B, D] (any row stride >= D) into ``image_cache`` / ``text_cache``
+    [N*B, D]; the int64 id vectors [B] into ``*_id_cache`` [N*B]; ``neighbor_tile_ids`` (int64) / ``neighbor_alphas`` (fp32)
+    [B, K] into their [N*B, K] caches.  Ids and neighbours may be None (ClipLoss, SigLipLoss); K may be 0."""
+    _req(image_features, torch.float32, "image_features"); _req(text_features, torch.float32, "text_features")
+    B, D = image_features.shape
+    if tuple(text_features.shape) != (B, D):
+        raise ValueError(f"group_cache_put: text_features {tuple(text_features.shape)} against image_features {(B, D)}")
+    G = int(N) * B
+    K = 0 if neighbor_tile_ids is None else int(neighbor_tile_ids.shape[1])
+    if K == 0:      # [B, 0] matrices carry nothing: the neighbour caches are not touched
+        neighbor_tile_ids = neighbor_alphas = neighbor_id_cache = neighbor_alpha_cache = None
+
+    def want(t, dtype, shape, name, optional=False):
+        if t is None:
+            if optional:
+                return
+            raise ValueError(f"group_cache_put: {name} is missing")
+        _req(t, dtype, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"group_cache_put: {name}: expected a contiguous {dtype} {shape}, got {tuple(t.shape)}")
+    want(image_cache, torch.float32, (G, D), "image_cache"); want(text_cache, torch.float32, (G, D), "text_cache")
+    for src, cache, dtype, shp, name in ((image_tile_ids, image_id_cache, torch.int64, (), "image_tile_ids"),
+                                         (text_tile_ids, text_id_cache, torch.int64, (), "text_tile_ids"),
+                                         (neighbor_tile_ids, neighbor_id_cache, torch.int64, (K,), "neighbor_tile_ids"),
+                                         (neighbor_alphas, neighbor_alpha_cache, torch.float32, (K,), "neighbor_alphas")):
+        want(src, dtype, (B,) + shp, name, optional=True)
+        if src is not None and (K > 0 or not shp):
+            want(cache, dtype, (G,) + shp, name + " cache")
+    check(_lib.lib().sc_group_cache_put(
+        image_features.data_ptr(), image_features.stride(0), text_features.data_ptr(), text_features.stride(0),
+        _ptr(image_tile_ids), _ptr(text_tile_ids), _ptr(neighbor_tile_ids), _ptr(neighbor_alphas), image_cache.data_ptr(),
+        text_cache.data_ptr(), _ptr(image_id_cache), _ptr(text_id_cache), _ptr(neighbor_id_cache), _ptr(neighbor_alpha_cache),
+        B, D, K, int(j), int(N), _stream()), "sc_group_cache_put")
+
+
 def siglip_loss(z, B, G, col0, scale, bias, rowpart, loss_out, dscale, dbias, hits3=None):
     check(_lib.lib().sc_siglip_loss(z.data_ptr(), B, G, col0, scale.data_ptr(), _ptr(bias), rowpart.data_ptr(),
                                     _ptr(loss_out), _ptr(dscale), _ptr(dbias), _ptr(hits3), _stream()),

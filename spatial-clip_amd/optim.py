@@ -1056,12 +1056,15 @@ class GradAccumulator:
     one streaming kernel (``ops.grad_accumulate``, 12 bytes per parameter) folds each micro-batch in with weight ``1/every``:
     the first of a group starts the sum, the last leaves ``sum + its own share`` in ``store.grad`` -- where the reducer, the
     clip and AdamW expect the gradient -- and does not write ``acc``.  ``acc`` is allocated on first use and only when
-    ``every > 1``; no producer kernel learns an accumulate mode."""
+    ``every > 1``; no producer kernel learns an accumulate mode.  ``scale`` replaces the weight ``1/every``: the cached-feature
+    form (``Trainer(accum_freq=N)``) folds at 1."""
 
-    def __init__(self, store, every: int):
+    def __init__(self, store, every: int, scale: Optional[float] = None):
         every = validate_accumulate_grad_batches(every)
         self.store, self.every = store, every
-        self.scale = 1.0 / every
+        # ``scale=1.0``: the cached-feature form (Trainer accum_freq): each micro-batch's gradient is already its share of the
+        # group loss, a mean over all N * B pairs
+        self.scale = 1.0 / every if scale is None else float(scale)
         self.acc: Optional[torch.Tensor] = None
         self.partial: Optional[torch.Tensor] = None     # 1024 fp64 sums of squares of the summed gradient (sumsq_partial())
         self._folded: List[Tuple[int, int]] = []        # ranges folded since the last hook() (sorted, disjoint)

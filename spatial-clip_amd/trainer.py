@@ -11,7 +11,9 @@ the launcher started, and reduces gradients with this package's bucketed all-red
 Loop semantics per step: training_step -> loss.backward() -> grad all-reduce (mean) ->
 clip_grad_norm_ -> AdamW.step -> scheduler.step().  With ``accumulate_grad_batches=N`` the part from the all-reduce on runs
 after every N-th batch and after the epoch's last one, on the sum of the group's gradients, each weighted 1/N
-(``optim.GradAccumulator``; DESIGN.md "Gradient accumulation").  Checkpoints (reference: ModelCheckpoint monitor ``val/R@1``,
+(``optim.GradAccumulator``; DESIGN.md "Gradient accumulation").  With ``accum_freq=N`` (open_clip's ``--accum-freq``; DESIGN.md
+section 4o) N micro-batches are ONE batch of N x B pairs: ``module.cached_group_step`` caches their features, evaluates the loss
+once and backpropagates each micro-batch from its rows of the feature gradients; n_batches // N steps per epoch.  Checkpoints (reference: ModelCheckpoint monitor ``val/R@1``,
 ``save_last``; configs/callbacks/default.yaml:8-14, gated by ``save_ckpt`` -> ``enable_checkpointing``,
 src/train.py:77-99) are written by rank 0 under ``default_root_dir/checkpoints``; ``fit(ckpt_path=...)`` resumes
 weights, optimiser moments, LR schedule and the step counter (src/train.py:119).  ``callbacks["weight_averaging"]`` (the
@@ -66,6 +68,48 @@ def resume_position(global_step: int, n_train: int, every: int):
     return epoch, (int(global_step) - epoch * spe) * int(every)
 
 
+def validate_accum_freq(value) -> int:
+    """``accum_freq`` (open_clip's ``--accum-freq``) as this build takes it: an integer >= 1 (1: no accumulation)."""
+    ok = isinstance(value, int) and not isinstance(value, bool) and value >= 1
+    if not ok:
+        raise ValueError(f"accum_freq={value!r}: an integer >= 1 is accepted (1 = every batch is its own optimiser step)")
+    return int(value)
+
+
+def group_steps_per_epoch(n_train: int, accum_freq: int) -> int:
+    """Optimiser steps of one epoch of ``n_train`` micro-batches under ``accum_freq``: open_clip's rule
+    (``num_batches_per_epoch = dataloader.num_batches // accum_freq``, open_clip_train/train.py:66): n_train // accum_freq."""
+    return int(n_train) // validate_accum_freq(accum_freq)
+
+
+def group_dropped_tail(n_train: int, accum_freq: int) -> int:
+    """Trailing micro-batches of an epoch that fill no group and are dropped (Lightning's ``accumulate_grad_batches`` steps on
+    them instead: ``accum_steps_after``)."""
+    return int(n_train) - group_steps_per_epoch(n_train, accum_freq) * int(accum_freq)
+
+
+def group_closes_after(n_train: int, accum_freq: int) -> List[bool]:
+    """Does training batch ``i`` (0-based within the epoch) close a group of ``accum_freq``, i.e. is it followed by the group's
+    loss, phase 2 and an optimiser step?  The dropped tail never does."""
+    N = validate_accum_freq(accum_freq)
+    used = group_steps_per_epoch(n_train, N) * N
+    return [i < used and (i + 1) % N == 0 for i in range(int(n_train))]
+
+
+def group_resume_position(global_step: int, n_train: int, accum_freq: int):
+    """(epoch to continue in, training batches of it to skip) for a checkpoint that counted ``global_step`` optimiser steps under
+    ``accum_freq``.  A step is taken only behind a whole group, so no checkpoint sits inside one; the dropped tail belongs to
+    the epoch it was dropped from."""
+    spe = max(group_steps_per_epoch(n_train, accum_freq), 1)
+    epoch = int(global_step) // spe
+    return epoch, (int(global_step) - epoch * spe) * int(accum_freq)
+
+
+def group_estimated_stepping_batches(n_train: int, accum_freq: int, epochs: int, max_steps: int = -1) -> int:
+    """``Trainer.estimated_stepping_batches`` under ``accum_freq``: optimiser steps, ``max_steps`` when it is set."""
+    return group_steps_per_epoch(n_train, accum_freq) * int(epochs) if max_steps == -1 else int(max_steps)
+
+
 class CheckpointCallback:
     """The slice of ``lightning.pytorch.callbacks.ModelCheckpoint`` that src/train.py reads back."""
 
@@ -88,7 +132,7 @@ class Trainer:
                  limit_train_batches: float = 1.0, limit_val_batches: float = 1.0, limit_test_batches: float = 1.0,
                  deterministic: bool = False, strategy: str = "auto", num_nodes: int = 1, sync_batchnorm: bool = False,
                  default_root_dir: Optional[str] = None, enable_checkpointing: bool = False, callbacks=None, logger=None,
-                 val_check_interval: Any = 1.0, accumulate_grad_batches: int = 1, **unused):
+                 val_check_interval: Any = 1.0, accumulate_grad_batches: int = 1, accum_freq: int = 1, **unused):
         if precision not in ("bf16-mixed", "bf16", "fp8-mixed", "fp8", "32", "32-true", 32):
             raise ValueError(f"precision {precision!r}: 'bf16-mixed' (bf16 MFMA GEMMs, fp32 accumulation / residual stream "
                              "/ master weights) or 'fp8-mixed' (e4m3 MFMA GEMMs in the transformer blocks on the same policy)")
@@ -106,6 +150,18 @@ class Trainer:
                              "gradient exchange reduce-scatters every backward and has no accumulating form; accepted: "
                              "accumulate_grad_batches=1 with it, or SC_GRAD_EXCHANGE=allreduce (the default) with any N >= 1")
         self.accumulator: Optional[GradAccumulator] = None      # built by fit() when accumulate_grad_batches > 1
+        # open_clip's --accum-freq (cached-feature accumulation): N micro-batches, ONE loss over N * B pairs
+        self.accum_freq = validate_accum_freq(accum_freq)
+        if self.accum_freq > 1:
+            if self.accumulate_grad_batches > 1:
+                raise ValueError(f"accum_freq={accum_freq} with accumulate_grad_batches={accumulate_grad_batches}: the two "
+                                 "forms of gradient accumulation do not nest; set one of them to 1")
+            if self.precision == "fp8":
+                raise ValueError(f"accum_freq={accum_freq} with precision={precision!r}: not supported (the caching pass would "
+                                 "advance the delayed e4m3 scaling); use 'bf16-mixed'")
+            if comm.grad_exchange_mode() == "sharded":
+                raise ValueError(f"accum_freq={accum_freq} with SC_GRAD_EXCHANGE=sharded: not supported (the group cache is "
+                                 "single-process and the sharded exchange has no accumulating form)")
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.gradient_clip_val = gradient_clip_val
         self.fast_dev_run = fast_dev_run
@@ -128,6 +184,7 @@ class Trainer:
         # ---- distributed: join the group the launcher described, or fail loudly
         want = _requested_world(devices, num_nodes)
         env_rank, env_local, env_W = comm.env_world()
+        self._check_accum_freq_world(max(env_W, want or 1, comm.world()[1]))    # before any group is joined
         if want is not None and want > 1 and env_W == 1 and not comm.is_dist():
             raise RuntimeError(
                 f"trainer.devices={devices} x num_nodes={num_nodes} asks for {want} ranks but this process was started "
@@ -168,6 +225,11 @@ class Trainer:
             if comm.grad_exchange_mode() == "sharded":
                 raise ValueError("callbacks.weight_averaging with SC_GRAD_EXCHANGE=sharded: not supported (a rank updates 1/W of "
                                  "every bucket); use SC_GRAD_EXCHANGE=allreduce (the default)")
+
+    def _check_accum_freq_world(self, world: int) -> None:
+        if self.accum_freq > 1 and world > 1:
+            raise ValueError(f"accum_freq={self.accum_freq} under a process group of {world} ranks: not supported (the group "
+                             "cache and the group loss are single-process); use accum_freq=1 or one process")
 
     def _validate(self, model, datamodule) -> Dict[str, float]:
         """Validation on the averaged weights once an average exists (``callbacks["weight_averaging"]``; Lightning's
@@ -220,7 +282,16 @@ class Trainer:
         n_train = self._limit(len(train), self.limit_train_batches)
         epochs = 1 if self.fast_dev_run else (self.max_epochs or 1)
         every = self.accumulate_grad_batches
-        self.estimated_stepping_batches = steps_per_epoch(n_train, every) * epochs if self.max_steps == -1 else self.max_steps
+        freq = self.accum_freq
+        if freq > 1:
+            self._check_accum_freq_world(comm.world()[1])
+            model.check_cached_accumulation(freq)       # DistillClipLoss / dist_net, fp8 net: ValueError
+            if n_train < freq:
+                raise ValueError(f"accum_freq={freq} with {n_train} training batches per epoch: not one group fills, no "
+                                 "optimiser step would ever be taken")
+            self.estimated_stepping_batches = group_estimated_stepping_batches(n_train, freq, epochs, self.max_steps)
+        else:
+            self.estimated_stepping_batches = steps_per_epoch(n_train, every) * epochs if self.max_steps == -1 else self.max_steps
         model.trainer = self
         net_prec = getattr(model.net, "precision", "bf16")
         if net_prec != self.precision:
@@ -252,12 +323,13 @@ class Trainer:
             if not os.path.isfile(ckpt_path):
                 raise FileNotFoundError(f"ckpt_path {ckpt_path!r} does not exist")
             self.global_step = self.load_checkpoint(ckpt_path, model, opt, sched)
-            start_epoch, resume_skip = resume_position(self.global_step, n_train, every)
+            start_epoch, resume_skip = (group_resume_position(self.global_step, n_train, freq) if freq > 1
+                                        else resume_position(self.global_step, n_train, every))
         # single process, bf16, FusedAdamW: the step can run as ONE hipGraph (SC_GRAPH=auto: only where the first eager steps
         # show the host as the bottleneck -- the reference's ViT-B-32 / batch-32 experiments; =1 always; =0 never)
         # (not an accumulated step: its launches differ from micro-batch to micro-batch)
         gstep = None
-        if every == 1 and reducer is None and graph.graph_mode() != "0" and hasattr(opt, "step_captured") and torch.cuda.is_available():
+        if every == 1 and freq == 1 and reducer is None and graph.graph_mode() != "0" and hasattr(opt, "step_captured") and torch.cuda.is_available():
             gstep = graph.GraphedTrainStep(model, opt, max_norm=self.gradient_clip_val, grad_scale=1.0 / W,
                                            policy="always" if graph.graph_mode() == "1" else "host_bound")
         self.graphed_step = gstep
@@ -270,8 +342,15 @@ class Trainer:
                                  "default all-reduce exchange, or accumulate_grad_batches=1)")
             accum = GradAccumulator(model.net.store, every)
             clipping = self.gradient_clip_val is not None and self.gradient_clip_val > 0
+        if freq > 1:
+            if reducer is not None:
+                raise ValueError(f"accum_freq={freq} under a process group of {W} ranks: not supported")
+            accum = model.group_accumulator(freq)       # optim.GradAccumulator at scale 1
+            clipping = self.gradient_clip_val is not None and self.gradient_clip_val > 0
+            n_train = group_steps_per_epoch(n_train, freq) * freq       # open_clip's epoch: the tail that fills no group is dropped
         self.accumulator = accum
         steps_after = accum_steps_after(n_train, every)
+        group: List[Dict[str, Any]] = []
         vci = self.val_check_interval
         val_every = 0 if self.fast_dev_run else (int(vci) if isinstance(vci, int) and not isinstance(vci, bool)
                                                  else (max(1, int(n_train * vci)) if vci < 1.0 else 0))
@@ -289,7 +368,19 @@ class Trainer:
                 if i < skip:
                     continue
                 batch = _to_device(batch, model.device)
-                if accum is not None:
+                if freq > 1:
+                    # cached-feature accumulation: the group keeps its micro-batches; behind the freq-th one, the group step
+                    # (phase 1, the loss of all freq * B pairs, phase 2 with the folds) and ONE clip / optimiser step
+                    group.append(batch)
+                    if len(group) < freq:
+                        self._val_in_epoch(model, datamodule, val_every, i, n_train, epoch)
+                        continue
+                    partial = accum.sumsq_partial() if clipping else None
+                    loss = model.cached_group_step(group, partial=partial)
+                    group = []
+                    with streams.chain_stream():
+                        opt.step(grad_scale=1.0, max_norm=self.gradient_clip_val, sumsq_partial=partial)
+                elif accum is not None:
                     # one micro-batch of a group: backward, fold its gradient into the running sum -- on the chain stream, behind
                     # the joins at the end of backward that opt.step relies on (side-stream weight gradients: SideScheduler.join;
                     # second tower: net._backward) -- and, behind the group's last one, the step on the summed gradient
