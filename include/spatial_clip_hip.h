@@ -568,6 +568,44 @@ int sc_lamb_trust(const float* slot_sums, long long n_slots, const int* tensor_s
                   int always_adapt, int trust_clip, float* trust, void* stream);
 int sc_lamb_apply(float* params, const float* exp_avg, const float* exp_avg_sq, long long n, const int* slot_tensor,
                   const float* hyper, const float* trust, int n_tensors, float eps, void* params_bf16, void* stream);
+/* Muon (K. Jordan 2024; the optimiser PyTorch 2.9+ ships under optim.Muon, whose code is the reference) for chosen 2-D tensors of
+ * the flat buffers,
+ * AdamW (sc_adamw_step_groups' update, bit for bit) for every other slot.  Per Muon tensor T of stored shape [r, c], group
+ * scalars {lr, wd}, ge = g * grad_scale * clip:
+ *   B = lerp(B, ge, 1 - mu);  U = nesterov ? lerp(ge, B, mu) : B            (the reference's lerp, both branches of it)
+ *   X = bf16(U) / max(||bf16(U)||_F, eps)                                     (norm finished in fp64, X rounded to bf16)
+ *   ns_steps times:  G = X X^T;  P = b G + c G G;  X = a X + P X              (r <= c; r > c: G = X^T X, X = a X + X P;
+ *                                                                              bf16 operands, fp32 accumulate, one rounding each)
+ *   p = p (1 - lr wd) - lr ratio[T] X
+ * One step is: sc_muon_momentum over every range, sc_muon_scale once, the Newton-Schulz products matrix by matrix through
+ * sc_gemm_bf16 (SC_EPI_BF16 for G, SC_EPI_F32 + sc_muon_axpby for the two products with an epilogue), sc_muon_apply over the
+ * pieces.  No atomics; the bits do not depend on how the buffer is cut into ranges.
+ *   slot_tensor  (DEVICE ints, one per 64-float slot of the RANGE): the Muon tensor of the slot, -1 for an AdamW slot, any
+ *                other value outside [0, n_tensors) for a slot that is neither read nor written;
+ *   tensor_info  (DEVICE ints, 4 per Muon tensor): {first slot, one past the last, first slot of the tensor in the compact
+ *                bf16 buffers, 0}; a Muon tensor has r, c multiples of 8 and therefore fills whole slots;
+ *   slot0        the slot of the flat buffer at which the range starts;
+ *   one_minus_momentum  the weight of B's lerp, rounded to fp32 from the double 1 - momentum as the reference rounds it (1 - 0.95f in
+ *                fp32 is another number); refused when it is not 1 - momentum to 1e-6;
+ *   ubuf / xbuf / obuf  compact bf16 buffers: tensor T's elements start at 64 * tensor_info[4 T + 2], row-major [r, c];
+ *   slot_sums    one float per slot of the range: sum of squares of the slot's bf16(U), 16 lanes in a fixed order.
+ * sc_muon_scale: one fixed-order fp64 sum per tensor over the WHOLE buffer's slot_sums (n_slots of them), norms[T] = the norm,
+ * xbuf = bf16(ubuf / max(norm, eps)).
+ * sc_muon_axpby: out = bf16(beta * cin + alpha * acc) over n elements (a positive multiple of 8): acc fp32, cin and out bf16,
+ * all 16-byte aligned; out must not overlap cin or acc.
+ * sc_muon_apply over a range: Muon slots as above (obuf = the NS result), AdamW slots with chunk_group / group_hyper of
+ * sc_adamw_step_groups.  n: a positive multiple of 64; 1 <= n_groups <= 256; 0 <= n_tensors <= 2^20 (0: no table is read);
+ * fp32 buffers 16-byte aligned.  A refusal sets sc_last_error and launches nothing. */
+int sc_muon_momentum(const float* grads, float* exp_avg, long long n, const int* slot_tensor, const int* tensor_info,
+                     int n_tensors, long long slot0, float momentum, float one_minus_momentum, int nesterov, float grad_scale,
+                     const float* norm_clip, void* ubuf, float* slot_sums, void* stream);
+int sc_muon_scale(const float* slot_sums, long long n_slots, const int* tensor_info, int n_tensors, float eps, const void* ubuf,
+                  void* xbuf, float* norms, void* stream);
+int sc_muon_axpby(const float* acc, const void* cin, void* out, long long n, float alpha, float beta, void* stream);
+int sc_muon_apply(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                  const unsigned char* chunk_group, const int* slot_tensor, const int* tensor_info, const float* ratio,
+                  int n_tensors, long long slot0, const void* obuf, const float* group_hyper, int n_groups, float beta1,
+                  float beta2, float eps, float grad_scale, const float* norm_clip, void* params_bf16, void* stream);
 /* The two halves of sc_grad_norm for an optimiser that owns 1/W of every gradient bucket (reduce-scatter ->
  * AdamW on the rank's shard -> all-gather; Lightning's DDP mean, configs/trainer/ddp.yaml:4, replaced): 1024 fp64 partial
  * sums of squares per contiguous piece of the shard, then -- after the caller has all-reduced (SUM) the concatenated

@@ -39,6 +39,7 @@ TARGET_MAP = {
     "timm.optim.lion.Lion": "spatial_clip_amd.optim.FusedLion",
     "timm.optim.Lamb": "spatial_clip_amd.optim.FusedLamb",
     "timm.optim.lamb.Lamb": "spatial_clip_amd.optim.FusedLamb",
+    "torch.optim.Muon": "spatial_clip_amd.optim.FusedMuon",
     "transformers.get_cosine_schedule_with_warmup": "spatial_clip_amd.optim.get_cosine_schedule_with_warmup",
     "lightning.pytorch.Trainer": "spatial_clip_amd.trainer.Trainer",
     "lightning.Trainer": "spatial_clip_amd.trainer.Trainer",

@@ -1102,6 +1102,107 @@ def lamb_apply(p, m, v, n, slot_tensor, hyper, trust, n_tensors, eps, p_bf16=Non
                                    n_tensors, float(eps), _ptr(p_bf16), _stream()), "sc_lamb_apply")
 
 
+def _muon_tables(what, n_slots, n_tensors, slot_tensor=None, tensor_info=None, slot_sums=None, ratio=None, norms=None):
+    """Dtype, device and size of the Muon tables that are given (``None`` is passed on as NULL, which the library refuses)."""
+    ok = 1 <= n_tensors <= (1 << 20)
+    for t, dtype, name, need in ((slot_tensor, torch.int32, "slot_tensor", n_slots), (tensor_info, torch.int32, "tensor_info", 4 * n_tensors),
+                                 (slot_sums, torch.float32, "slot_sums", n_slots), (ratio, torch.float32, "ratio", n_tensors),
+                                 (norms, torch.float32, "norms", n_tensors)):
+        if t is None:
+            continue
+        _req(t, dtype, name)
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if ok and n_slots > 0 and t.numel() < need:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, {need} are needed")
+
+
+def _muon_bf16(what, t, name, need):
+    if t is None:
+        return
+    _req(t, torch.bfloat16, name)
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    if t.numel() < need:
+        raise ValueError(f"{what}: {name} holds {t.numel()} elements, {need} are needed")
+
+
+def muon_momentum(g, m, n, slot_tensor, tensor_info, n_tensors, slot0, momentum, nesterov, grad_scale, norm_clip, ubuf, slot_sums,
+                  compact_slots):
+    """Muon, first pass over flat[:n] (``sc_muon_momentum``): on the slots of a Muon tensor ``m = lerp(m, ge, 1 - momentum)``,
+    ``bf16(U)`` into the compact buffer ``ubuf`` and the slot's sum of squares of it into ``slot_sums`` (fp32, one per slot of
+    the range); every other slot is neither read nor written.  ``slot_tensor`` (int32, one per slot of the range),
+    ``tensor_info`` (int32 [n_tensors, 4]: first slot, one past the last, first compact slot, 0), ``slot0``: the slot at which
+    the range starts; ``compact_slots``: what the caller's tables address in ``ubuf`` at the most (host-side size check)."""
+    n, n_tensors = int(n), int(n_tensors)
+    _muon_tables("muon_momentum", n // 64, n_tensors, slot_tensor=slot_tensor, tensor_info=tensor_info, slot_sums=slot_sums)
+    _muon_bf16("muon_momentum", ubuf, "ubuf", 64 * int(compact_slots))
+    for t, name in ((g, "g"), (m, "m")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"muon_momentum: {name} holds {t.numel()} floats, n = {n}")
+    check(_lib.lib().sc_muon_momentum(g.data_ptr(), m.data_ptr(), n, _ptr(slot_tensor), _ptr(tensor_info), n_tensors, int(slot0),
+                                      float(momentum), 1.0 - float(momentum), int(bool(nesterov)), float(grad_scale), _ptr(norm_clip),
+                                      _ptr(ubuf),
+                                      _ptr(slot_sums), _stream()), "sc_muon_momentum")
+
+
+def muon_scale(slot_sums, n_slots, tensor_info, n_tensors, eps, ubuf, xbuf, norms, compact_slots):
+    """Muon, between the passes (``sc_muon_scale``): each tensor's Frobenius norm from the slot sums of the WHOLE buffer in fp64
+    (fixed order) into ``norms`` and ``xbuf = bf16(ubuf / max(norm, eps))`` (compact bf16 buffers)."""
+    n_slots, n_tensors = int(n_slots), int(n_tensors)
+    _muon_tables("muon_scale", n_slots, n_tensors, tensor_info=tensor_info, slot_sums=slot_sums, norms=norms)
+    _muon_bf16("muon_scale", ubuf, "ubuf", 64 * int(compact_slots))
+    _muon_bf16("muon_scale", xbuf, "xbuf", 64 * int(compact_slots))
+    check(_lib.lib().sc_muon_scale(_ptr(slot_sums), n_slots, _ptr(tensor_info), n_tensors, float(eps), _ptr(ubuf), _ptr(xbuf),
+                                   _ptr(norms), _stream()), "sc_muon_scale")
+
+
+def muon_axpby(acc, cin, out, n, alpha, beta):
+    """``out[:n] = bf16(beta * cin[:n] + alpha * acc[:n])`` (``sc_muon_axpby``): the epilogue of a Newton-Schulz product whose fp32
+    accumulators ``gemm(..., EPI_F32, ...)`` left in ``acc``; ``cin`` and ``out`` bf16, distinct buffers."""
+    n = int(n)
+    if acc is not None:
+        _req(acc, torch.float32, "acc")
+        if acc.numel() < n:
+            raise ValueError(f"muon_axpby: acc holds {acc.numel()} floats, n = {n}")
+    _muon_bf16("muon_axpby", cin, "cin", n)
+    _muon_bf16("muon_axpby", out, "out", n)
+    if out is not None and cin is not None and out.data_ptr() == cin.data_ptr():
+        raise ValueError("muon_axpby: out must not be cin")
+    check(_lib.lib().sc_muon_axpby(_ptr(acc), _ptr(cin), _ptr(out), n, float(alpha), float(beta), _stream()), "sc_muon_axpby")
+
+
+def muon_apply(p, g, m, v, n, chunk_group, slot_tensor, tensor_info, ratio, n_tensors, slot0, obuf, group_hyper, n_groups, beta1,
+               beta2, eps, grad_scale, norm_clip, p_bf16=None, compact_slots=0):
+    """Muon, last pass over flat[:n] (``sc_muon_apply``): ``p = p (1 - lr wd) - lr ratio[T] O`` on the slots of Muon tensor T
+    (``obuf``: the Newton-Schulz result, compact bf16), the update of ``adamw_step_groups`` on the slots marked -1, nothing
+    on a slot marked otherwise.  ``chunk_group`` / ``group_hyper`` as for ``adamw_step_groups``."""
+    n, n_tensors, n_groups = int(n), int(n_tensors), int(n_groups)
+    _muon_tables("muon_apply", n // 64, max(n_tensors, 1), slot_tensor=slot_tensor,
+                 tensor_info=tensor_info if n_tensors else None, ratio=ratio if n_tensors else None)
+    if n_tensors:
+        _muon_bf16("muon_apply", obuf, "obuf", 64 * int(compact_slots))
+    if chunk_group is not None:
+        _req(chunk_group, torch.uint8, "chunk_group")
+        if n > 0 and chunk_group.numel() < n // 64:
+            raise ValueError(f"muon_apply: chunk_group holds {chunk_group.numel()} slots, the range has {n // 64}")
+    if group_hyper is not None:
+        _req(group_hyper, torch.float32, "group_hyper")
+        if 1 <= n_groups <= 256 and group_hyper.numel() < 2 + 2 * n_groups:
+            raise ValueError(f"muon_apply: group_hyper holds {group_hyper.numel()} floats, {n_groups} groups need {2 + 2 * n_groups}")
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _req(t, torch.float32, name)
+        if t.numel() < n:
+            raise ValueError(f"muon_apply: {name} holds {t.numel()} floats, n = {n}")
+    if p_bf16 is not None and p_bf16.numel() < n:
+        raise ValueError(f"muon_apply: the bf16 mirror holds {p_bf16.numel()} elements, n = {n}")
+    check(_lib.lib().sc_muon_apply(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, _ptr(chunk_group), _ptr(slot_tensor),
+                                   _ptr(tensor_info), _ptr(ratio), n_tensors, int(slot0), _ptr(obuf), _ptr(group_hyper), n_groups,
+                                   float(beta1), float(beta2), float(eps), float(grad_scale), _ptr(norm_clip), _ptr(p_bf16),
+                                   _stream()), "sc_muon_apply")
+
+
 def cast_transpose_batched(master, desc, tile_prefix, n, total_tiles, mirror_bf16=None):
     check(_lib.lib().sc_cast_transpose_batched(master.data_ptr(), _ptr(mirror_bf16), desc.data_ptr(),
                                                tile_prefix.data_ptr(), n, total_tiles, _stream()),

@@ -9,7 +9,9 @@ bf16 compute-copy refresh.  ``params`` may also be torch's other form, a list of
 launches ``ops.adamw_step_groups``, one streaming launch per range with a per-slot group table.
 ``FusedLion(params, lr, betas, weight_decay)`` takes the kwargs of ``lion_pytorch.Lion`` / ``timm.optim.Lion`` and runs the
 same step forms with one moment (``ops.lion_step*``); ``FusedLamb`` takes the kwargs of ``timm.optim.Lamb``
-and runs them with per-tensor trust ratios (``ops.lamb_*``, section 4m); all three are ``_FlatOptimizer`` with their own launches.
+and runs them with per-tensor trust ratios (``ops.lamb_*``, section 4m); ``FusedMuon`` takes the kwargs of ``torch.optim.Muon``,
+orthogonalises the block Linears' updates by Newton-Schulz GEMMs and runs AdamW on the rest (``ops.muon_*``, section 4p); all four are
+``_FlatOptimizer`` with their own launches.
 ``WeightAverager`` keeps an averaged copy of the weights (Lightning's ``EMAWeightAveraging`` / ``WeightAveraging``) in a flat
 buffer of its own, updated behind every piece of those step forms (``ops.weight_average*``, section 4n).
 ``get_cosine_schedule_with_warmup`` reproduces transformers' LambdaLR schedule
@@ -182,13 +184,19 @@ class _FlatOptimizer:
         self.param_groups = out
         if len(out) > 1:
             self.chunk_group = slot_table(store, [g["param_names"] for g in out]).to(store.device)
-            n = self._group_hyper_floats(len(out))        # allocated here, on the stream the optimiser is built on, not inside a step
-            cuda = torch.device(store.device).type == "cuda"
-            self.group_hyper = torch.zeros(n, dtype=torch.float32, device=store.device)
-            self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=store.device)
-            for _ in range(4):
-                host = torch.zeros(n, dtype=torch.float32)
-                self._group_stage.append([host.pin_memory() if cuda else host, None])
+            self._alloc_group_hyper(len(out))
+
+    def _alloc_group_hyper(self, n_groups: int) -> None:
+        """The device scalar tables of ``n_groups`` groups and their pinned staging ring: allocated where the optimiser is
+        built, on the stream it is built on, not inside a step."""
+        dev = self.store.device
+        n = self._group_hyper_floats(n_groups)
+        cuda = torch.device(dev).type == "cuda"
+        self.group_hyper = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=dev)
+        for _ in range(4):
+            host = torch.zeros(n, dtype=torch.float32)
+            self._group_stage.append([host.pin_memory() if cuda else host, None])
 
     def _refresh_group_hyper(self, behind: bool = False) -> torch.Tensor:
         """Two or more groups: {1 - beta1^step, sqrt(1 - beta2^step)} and every group's {lr, weight_decay} for the step about
@@ -437,14 +445,15 @@ class _FlatOptimizer:
                 "param_groups": [{k: v_ for k, v_ in g.items() if k != "params"} for g in self.param_groups]}
 
     def _check_kind(self, sd) -> None:
-        """A checkpoint of another optimiser kind ("adamw", "lion", "lamb") is refused.  The kind is the "optimizer" entry; an
+        """A checkpoint of another optimiser kind ("adamw", "lion", "lamb", "muon") is refused.  The kind is the "optimizer" entry; an
         AdamW file carries none (it was written before that entry existed, and still is) and is known by its second moment."""
         mine = self.KIND or "adamw"
         has_sq = "exp_avg_sq" in sd
         theirs = sd.get("optimizer", "adamw" if has_sq else "lion")
         if theirs != mine or has_sq != ("exp_avg_sq" in self.STATE):
             other = theirs if theirs != mine else ("adamw" if has_sq else "lion")
-            kinds = "AdamW and Lion" if {mine, other} == {"adamw", "lion"} else "AdamW, Lion and LAMB"
+            kinds = ("AdamW and Lion" if {mine, other} == {"adamw", "lion"} else
+                     "AdamW, Lion, LAMB and Muon" if "muon" in (mine, other) else "AdamW, Lion and LAMB")
             raise ValueError(f"{self.NAME}.load_state_dict: the state dict (keys {sorted(k for k in sd if k != 'param_groups')}) is "
                              f"that of an {other!r} optimiser; this one is {mine!r} and keeps {list(self.STATE)}.  {kinds} "
                              "states do not convert into each other")
@@ -635,13 +644,7 @@ class FusedLamb(_FlatOptimizer):
         self.slot_sums = torch.zeros(2 * (st.total // 64), dtype=torch.float32, device=dev)     # {sum p^2, sum u^2} per slot
         self.trust = torch.ones(len(names), dtype=torch.float32, device=dev)                    # r of the last step, per tensor
         if self.group_hyper is None:        # one group: the same table and staging ring as with many (_init_groups)
-            n = self._group_hyper_floats(1)
-            cuda = torch.device(dev).type == "cuda"
-            self.group_hyper = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._group_hyper_behind = torch.zeros(n, dtype=torch.float32, device=dev)
-            for _ in range(4):
-                host = torch.zeros(n, dtype=torch.float32)
-                self._group_stage.append([host.pin_memory() if cuda else host, None])
+            self._alloc_group_hyper(1)
 
     def _uses_table(self) -> bool:
         return True
@@ -674,6 +677,277 @@ class FusedLamb(_FlatOptimizer):
         m, v = moments
         ops.lamb_apply(st.master[lo:hi], m, v, hi - lo, self.slot_tensor[lo // 64:], table, self.trust, len(self.tensor_names),
                        self.param_groups[0]["eps"], st.master_bf16[lo:hi])
+
+
+MUON_LEAVES = ("attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight")
+MUON_ADJUST_LR = (None, "original", "match_rms_adamw")
+
+
+def is_muon_name(name: str) -> bool:
+    """The default rule: the four Linear weights of a transformer block of any tower -- a state-dict name that ends in one of
+    ``MUON_LEAVES`` directly under a ``resblocks.<i>.``."""
+    for leaf in MUON_LEAVES:
+        if name.endswith("." + leaf):
+            parts = name[:-len(leaf) - 1].split(".")
+            return len(parts) >= 2 and parts[-2] == "resblocks" and parts[-1].isdigit()
+    return False
+
+
+def muon_shape_ok(shape) -> bool:
+    """What the Newton-Schulz GEMMs take: a 2-D tensor, both dimensions positive multiples of 8."""
+    return len(shape) == 2 and all(int(s) > 0 and int(s) % 8 == 0 for s in shape)
+
+
+def muon_adjust_ratio(adjust_lr_fn: Optional[str], shape) -> float:
+    """``lr_adj / lr`` of ``torch.optim._muon._adjust_lr`` for a parameter of ``shape``."""
+    r, c = int(shape[0]), int(shape[1])
+    if adjust_lr_fn == "match_rms_adamw":
+        return 0.2 * math.sqrt(max(r, c))
+    return math.sqrt(max(1, r / c))
+
+
+def muon_param_groups(named_parameters, lr: Optional[float] = None, weight_decay: Optional[float] = None,
+                      adamw_lr: Optional[float] = None, adamw_weight_decay: Optional[float] = None) -> List[Dict[str, Any]]:
+    """The default split of ``FusedMuon``: the block Linears (``is_muon_name``, shapes the kernel takes) in a group with
+    ``use_muon=True``, every other tensor -- embeddings, ``visual.proj`` / ``text_projection``, the gene-MLP, LayerNorm, biases,
+    ``logit_scale`` / ``logit_bias`` -- in one with ``use_muon=False``.  ``named_parameters``: ``(name, tensor)`` pairs, names
+    looked up in the ParamStore; a parameter with ``requires_grad=False`` is left out.  ``lr`` / ``weight_decay`` (and the
+    ``adamw_*`` pair for the second group) are written into the groups when given; an empty group is dropped."""
+    muon: Dict[str, Any] = {"params": [], "param_names": [], "use_muon": True}
+    rest: Dict[str, Any] = {"params": [], "param_names": [], "use_muon": False}
+    for key, value, g in (("lr", lr, muon), ("weight_decay", weight_decay, muon), ("lr", adamw_lr, rest),
+                          ("weight_decay", adamw_weight_decay, rest)):
+        if value is not None:
+            g[key] = float(value)
+    for name, p in named_parameters:
+        if isinstance(p, torch.nn.Parameter) and not p.requires_grad:
+            continue
+        name = _reference_name(name, p)
+        g = muon if is_muon_name(name) and muon_shape_ok(tuple(p.shape)) else rest
+        g["params"].append(p)
+        g["param_names"].append(name)
+    return [g for g in (muon, rest) if g["params"]]
+
+
+def muon_newton_schulz(x0: torch.Tensor, x1: torch.Tensor, lo: int, r: int, c: int, gbuf: torch.Tensor, pbuf: torch.Tensor,
+                       acc: torch.Tensor, ns_steps: int, coefficients) -> torch.Tensor:
+    """``ns_steps`` Newton-Schulz iterations on the matrix [r, c] at element ``lo`` of the compact bf16 buffers: X from ``x0`` to
+    ``x1`` and back, never in place; returns the buffer that holds the result (``x1`` for an odd ``ns_steps``).  Three products
+    per iteration through ``ops.gemm``; none needs a transpose, because G and P are symmetric: for r <= c ``G = X X^T`` (NT),
+    ``G G`` (NT) and ``P X`` as the TN product with At = P; for r > c, where torch works on X^T, ``G = X_s^T X_s`` is the TN
+    product of the stored matrix with itself and ``X_s P`` the NT product with B = P.  The two products with an epilogue leave
+    fp32 accumulators (``EPI_F32``) in ``acc`` (r * c floats) that ``ops.muon_axpby`` combines with ``beta Cin`` and rounds once.
+    ``gbuf`` / ``pbuf``: ``min(r, c)^2`` bf16 each."""
+    m = min(r, c)
+    a, b, cc = coefficients
+    g, p = gbuf[:m * m].view(m, m), pbuf[:m * m].view(m, m)
+    acc_mm, acc_x = acc[:m * m].view(m, m), acc[:r * c].view(r, c)
+    bufs = (x0, x1)
+    for it in range(ns_steps):
+        x = bufs[it & 1][lo:lo + r * c].view(r, c)
+        y = bufs[1 - (it & 1)][lo:lo + r * c].view(r, c)
+        if r > c:
+            ops.gemm(ops.TN, ops.EPI_BF16, x, x, g, M=c, N=c, K=r)
+        else:
+            ops.gemm(ops.NT, ops.EPI_BF16, x, x, g, M=r, N=r, K=c)
+        ops.gemm(ops.NT, ops.EPI_F32, g, g, acc_mm, M=m, N=m, K=m)
+        ops.muon_axpby(acc_mm, g, p, m * m, cc, b)
+        if r > c:
+            ops.gemm(ops.NT, ops.EPI_F32, x, p, acc_x, M=r, N=c, K=c)
+        else:
+            ops.gemm(ops.TN, ops.EPI_F32, p, x, acc_x, M=r, N=c, K=r)
+        ops.muon_axpby(acc_x, x, y, r * c, 1.0, a)
+    return x1 if ns_steps & 1 else x0
+
+
+class FusedMuon(_FlatOptimizer):
+    """Muon for the hidden matrices, AdamW for everything else, in one object.  The first nine arguments are the keywords and
+    defaults of ``torch.optim.Muon`` (torch 2.10; its code, ``torch/optim/_muon.py``, is the reference): per Muon tensor a
+    momentum buffer (``exp_avg``), ``ns_steps`` Newton-Schulz iterations on the bf16 update in the MFMA GEMMs of ``ops.gemm``
+    (matrix by matrix; fp32 accumulators, one rounding per product) and ``p = p (1 - lr wd) - lr_adj O``.  The ``adamw_*`` arguments belong to the other
+    part (``None``: the Muon value), which is ``FusedAdamW``'s grouped update bit for bit.  ``params``: a plain parameter list,
+    split by the default rule (``muon_param_groups``), or group dicts; a dict may carry ``use_muon: bool``, one without it is split
+    by the default rule.  ``use_muon=True`` is accepted for 2-D tensors whose two dimensions are multiples of 8.  A step is
+    ``ops.muon_momentum`` over every trainable range, ``ops.muon_scale``, ``_newton_schulz`` per matrix (``_before_pieces``),
+    then ``ops.muon_apply`` over the pieces of the step form.  Parameter groups, locked towers,
+    accumulation, weight averaging, the overlapped and the graph-captured step are ``FusedAdamW``'s, on the same code; the
+    sharded gradient exchange is refused."""
+    NAME = "FusedMuon"
+    STATE = ("exp_avg", "exp_avg_sq")
+    KIND = "muon"
+    SHARDABLE = False
+    OFF_ONLY = {"maximize": (False,), "foreach": (None, False)}
+    MUON_GROUP_KEYS = ("momentum", "nesterov", "ns_steps", "ns_coefficients", "adjust_lr_fn")
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, weight_decay: float = 0.1, momentum: float = 0.95,
+                 nesterov: bool = True, ns_coefficients=(3.4445, -4.7750, 2.0315), eps: float = 1e-7, ns_steps: int = 5,
+                 adjust_lr_fn: Optional[str] = None, adamw_lr: Optional[float] = None, adamw_betas=(0.9, 0.999),
+                 adamw_eps: float = 1e-8, adamw_weight_decay: Optional[float] = None, **options):
+        for key, value in options.items():
+            if key not in self.OFF_ONLY:
+                raise ValueError(f"FusedMuon: unknown keyword {key!r}; accepted: lr, weight_decay, momentum, nesterov, "
+                                 "ns_coefficients, eps, ns_steps, adjust_lr_fn, adamw_lr, adamw_betas, adamw_eps, "
+                                 f"adamw_weight_decay and (off only) {list(self.OFF_ONLY)}")
+            if not any(value is off for off in self.OFF_ONLY[key]):
+                raise ValueError(f"FusedMuon: {key}={value!r} is not supported; only {key}={self.OFF_ONLY[key][0]!r} is")
+        if isinstance(ns_steps, bool) or not isinstance(ns_steps, int) or not 1 <= ns_steps <= 99:
+            raise ValueError(f"FusedMuon: ns_steps={ns_steps!r}: an integer from 1 to 99 is expected")
+        if adjust_lr_fn not in MUON_ADJUST_LR:
+            raise ValueError(f"FusedMuon: adjust_lr_fn={adjust_lr_fn!r}: one of {list(MUON_ADJUST_LR)} is expected")
+        if not isinstance(nesterov, bool):
+            raise ValueError(f"FusedMuon: nesterov={nesterov!r}: True or False is expected")
+        if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum <= 1.0:
+            raise ValueError(f"FusedMuon: momentum={momentum!r}: a float from 0 to 1 is expected")
+        try:
+            coeffs = tuple(float(x) for x in ns_coefficients)
+        except TypeError:
+            coeffs = ()
+        if len(coeffs) != 3 or not all(math.isfinite(x) for x in coeffs):
+            raise ValueError(f"FusedMuon: ns_coefficients={ns_coefficients!r}: three finite floats are expected")
+        if not (isinstance(eps, (int, float)) and eps > 0):
+            raise ValueError(f"FusedMuon: eps={eps!r}: a positive float is expected")
+        self.momentum, self.nesterov, self.ns_coefficients = float(momentum), nesterov, coeffs
+        self.muon_eps, self.ns_steps, self.adjust_lr_fn = float(eps), ns_steps, adjust_lr_fn
+        own = {"momentum": self.momentum, "nesterov": nesterov, "ns_steps": ns_steps, "ns_coefficients": coeffs,
+               "adjust_lr_fn": adjust_lr_fn}
+        rest_lr = lr if adamw_lr is None else adamw_lr
+        rest_wd = weight_decay if adamw_weight_decay is None else adamw_weight_decay
+        params = list(params)
+        if any(isinstance(g, Mapping) for g in params) and not all(isinstance(g, Mapping) for g in params):
+            raise ValueError("FusedMuon: params mixes parameters and group dicts; pass either an iterable of parameters or an "
+                             "iterable of {'params': [...], ...} dicts")
+        if not params or not isinstance(params[0], Mapping):
+            stores = {id(getattr(p, "_sc_store", None)): getattr(p, "_sc_store", None) for p in params}
+            if len(stores) != 1 or None in stores.values():
+                raise ValueError("FusedMuon needs the parameters of exactly one SpatialClipNet (flat ParamStore)")
+            if len(params) != len(next(iter(stores.values())).specs):
+                raise ValueError("FusedMuon updates the whole flat buffer: pass all parameters (reference passes "
+                                 "self.parameters() un-grouped)")
+            params = [{"params": params}]
+        groups, kinds = [], []
+        for gi, g in enumerate(params):
+            for key in self.MUON_GROUP_KEYS:
+                if key in g:
+                    value = tuple(float(x) for x in g[key]) if key == "ns_coefficients" else g[key]
+                    if value != own[key]:
+                        raise ValueError(f"FusedMuon: parameter group {gi} sets {key}={g[key]!r}; per-group {key} is not "
+                                         f"supported (the optimiser's is {own[key]!r})")
+            if "params" not in g:
+                raise ValueError(f"FusedMuon: parameter group {gi} has no 'params'")
+            ps = g["params"]
+            ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            names = []
+            for p in ps:
+                st = getattr(p, "_sc_store", None)
+                if st is None:
+                    raise ValueError(f"FusedMuon: parameter group {gi} holds a tensor of shape {tuple(getattr(p, 'shape', ()))} "
+                                     "that is no parameter of a SpatialClipNet (flat ParamStore)")
+                names.append(_reference_name("", p))
+            use = g.get("use_muon")
+            if use is not None and not isinstance(use, bool):
+                raise ValueError(f"FusedMuon: parameter group {gi} sets use_muon={use!r}: True or False is expected")
+            if use is True:
+                for n, p in zip(names, ps):
+                    if not muon_shape_ok(tuple(p.shape)):
+                        raise ValueError(f"FusedMuon: parameter group {gi} sets use_muon=True for {n} of shape {tuple(p.shape)}; "
+                                         "Muon takes 2-D tensors whose two dimensions are multiples of 8")
+            pick = [use if use is not None else (is_muon_name(n) and muon_shape_ok(tuple(p.shape))) for n, p in zip(names, ps)]
+            base = {k: v for k, v in g.items() if k not in ("params", "param_names", "use_muon") + self.MUON_GROUP_KEYS}
+            for kind in (True, False):
+                part = [(n, p) for n, p, k in zip(names, ps, pick) if k is kind]
+                if not part and (ps or kind):       # an input group without parameters goes through once, to the base's refusal
+                    continue
+                new = dict(base)
+                new["params"], new["param_names"] = [p for _, p in part], [n for n, _ in part]
+                new.setdefault("lr", lr if kind else rest_lr)
+                new.setdefault("weight_decay", weight_decay if kind else rest_wd)
+                groups.append(new)
+                kinds.append(kind)
+        super().__init__(groups, lr, adamw_betas, adamw_eps, weight_decay)
+        for g, kind in zip(self.param_groups, kinds):
+            g["use_muon"] = kind
+        self._build_tables()
+
+    def _build_tables(self) -> None:
+        """The per-slot and per-tensor tables and the scratch buffers, over the trainable Muon tensors only: a locked matrix is
+        no tensor, gets no momentum and no Newton-Schulz iteration."""
+        st = self.store
+        dev = st.device
+        n_slots = st.total // 64
+        if self.chunk_group is None:        # one group: the same tables and staging ring as with many (_init_groups)
+            self.chunk_group = slot_table(st, [self.param_groups[0]["param_names"]]).to(dev)
+            self._alloc_group_hyper(1)
+        trainable = set(st.trainable_names())
+        names = sorted((n for g in self.param_groups if g["use_muon"] for n in g["param_names"] if n in trainable),
+                       key=lambda n: st.by_name[n].offset)
+        self.muon_names = names
+        slot_tensor = torch.full((n_slots,), -1, dtype=torch.int32)     # -1: an AdamW slot
+        info = torch.zeros((max(len(names), 1), 4), dtype=torch.int32)
+        ratio = torch.ones(max(len(names), 1), dtype=torch.float32)
+        shapes: List[Tuple[int, int]] = []
+        x_slot = 0
+        for ti, n in enumerate(names):
+            sp = st.by_name[n]
+            lo, k = sp.offset // 64, sp.numel // 64
+            slot_tensor[lo:lo + k] = ti
+            info[ti, 0], info[ti, 1], info[ti, 2] = lo, lo + k, x_slot
+            ratio[ti] = muon_adjust_ratio(self.adjust_lr_fn, sp.shape)
+            shapes.append((int(sp.shape[0]), int(sp.shape[1])))
+            x_slot += k
+        self.compact_slots = x_slot
+        self.muon_shapes = shapes                    # [r, c] of every Muon tensor, in buffer order
+        self.slot_tensor_host, self.tensor_info_host = slot_tensor, info
+        self.slot_tensor, self.tensor_info, self.ratio = slot_tensor.to(dev), info.to(dev), ratio.to(dev)
+        bf = torch.bfloat16
+        self.x0 = torch.zeros(max(64 * x_slot, 64), dtype=bf, device=dev)      # X ping
+        self.x1 = torch.zeros(max(64 * x_slot, 64), dtype=bf, device=dev)      # bf16(U), then X pong
+        mm = max([min(r, c) ** 2 for r, c in shapes] + [64])
+        self.gbuf = torch.zeros(mm, dtype=bf, device=dev)                      # G and P of the matrix in flight
+        self.pbuf = torch.zeros(mm, dtype=bf, device=dev)
+        self.acc = torch.zeros(max([r * c for r, c in shapes] + [64]), dtype=torch.float32, device=dev)     # fp32 accumulators of a product
+        self.slot_sums = torch.zeros(n_slots, dtype=torch.float32, device=dev)
+        self.norms = torch.zeros(max(len(names), 1), dtype=torch.float32, device=dev)      # ||bf16(U)|| of the last step
+
+    def _uses_table(self) -> bool:
+        return True
+
+    def _group_hyper_floats(self, n_groups: int) -> int:
+        return 2 + 2 * n_groups
+
+    def _fill_group_hyper(self, host: torch.Tensor) -> None:
+        g0 = self.param_groups[0]
+        ops.adamw_groups_hyper_host([g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
+                                    g0["betas"][0], g0["betas"][1], self.step_count, host)
+
+    def _obuf(self) -> torch.Tensor:
+        return self.x1 if self.ns_steps & 1 else self.x0
+
+    def _before_pieces(self, grad_scale, clip, table) -> None:
+        n_mu = len(self.muon_names)
+        if n_mu == 0:
+            return
+        st = self.store
+        for k, (lo, hi) in enumerate(self.ranges):
+            m, _ = self._moments(k, lo, hi)
+            ops.muon_momentum(st.grad[lo:hi], m, hi - lo, self.slot_tensor[lo // 64:], self.tensor_info, n_mu, lo // 64,
+                              self.momentum, self.nesterov, grad_scale, clip, self.x1, self.slot_sums[lo // 64:],
+                              self.compact_slots)
+        ops.muon_scale(self.slot_sums, st.total // 64, self.tensor_info, n_mu, self.muon_eps, self.x1, self.x0, self.norms,
+                       self.compact_slots)
+        for ti in range(n_mu):
+            self._newton_schulz(ti)
+
+    def _newton_schulz(self, ti: int) -> None:
+        r, c = self.muon_shapes[ti]
+        muon_newton_schulz(self.x0, self.x1, int(self.tensor_info_host[ti, 2]) * 64, r, c, self.gbuf, self.pbuf, self.acc,
+                           self.ns_steps, self.ns_coefficients)
+
+    def _update_groups(self, lo, hi, moments, grad_scale, clip, table) -> None:
+        st, g = self.store, self.param_groups[0]
+        m, v = moments
+        ops.muon_apply(st.master[lo:hi], st.grad[lo:hi], m, v, hi - lo, self.chunk_group[lo // 64:], self.slot_tensor[lo // 64:],
+                       self.tensor_info, self.ratio, len(self.muon_names), lo // 64, self._obuf(), table, len(self.param_groups),
+                       g["betas"][0], g["betas"][1], g["eps"], grad_scale, clip, st.master_bf16[lo:hi], self.compact_slots)
 
 
 def slot_table(store, group_names: Sequence[Sequence[str]]) -> torch.Tensor:
