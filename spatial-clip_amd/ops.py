@@ -644,20 +644,67 @@ def pack_rows(feat: torch.Tensor, ids_a: Optional[torch.Tensor], ids_b: Optional
     return out
 
 
+def _req_buf(what: str, t: torch.Tensor, dtype, n: int, name: str) -> None:
+    """What a raw pointer of the loss kernels stands for: a contiguous device tensor of ``dtype`` with at least ``n`` elements
+    (host shape arithmetic only: nothing is launched and nothing synchronises)."""
+    _req(t, dtype, name)
+    if not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of at least {n} elements, got shape "
+                         f"{tuple(t.shape)}, strides {tuple(t.stride())}")
+
+
+def _req_scalar(what: str, t: Optional[torch.Tensor], name: str, optional: bool = False, exact: bool = True) -> None:
+    """A device scalar: fp32, one element (``exact``) or a slot of at least one element the kernel writes its result to."""
+    if t is None:
+        if optional:
+            return
+        raise ValueError(f"{what}: {name} is missing")
+    _req(t, torch.float32, name)
+    if (t.numel() != 1) if exact else (t.numel() < 1 or not t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a one-element fp32 tensor, got shape {tuple(t.shape)}")
+
+
+def _req_dims(what: str, **dims) -> None:
+    for k, v in dims.items():
+        if int(v) != v or v < 0:
+            raise ValueError(f"{what}: {k} must be a non-negative int, got {v!r}")
+
+
+def _req_labels(what: str, lab_col, lab_w, B: int, nlab: int) -> None:
+    _req_buf(what, lab_col, torch.int32, 2 * B * nlab, "lab_col")
+    _req_buf(what, lab_w, torch.float32, 2 * B * nlab, "lab_w")
+
+
 def neighbor_join(all_img_ids, all_txt_ids, nbr_ids, nbr_alpha, B, G, K, rank, alpha_scale, lab_col, lab_w):
-    for t_, n in ((all_img_ids, "all_image_tile_ids"), (all_txt_ids, "all_text_tile_ids"), (nbr_ids, "neighbor_tile_ids")):
-        _req(t_, torch.int64, n)
-    _req(nbr_alpha, torch.float32, "neighbor_alphas")
+    """Sparse soft labels lab_col / lab_w [2, B, K + 1] from the tile-id join (``sc_neighbor_join``): the gathered id vectors hold
+    G int64 ids, ``nbr_ids`` (int64) and ``nbr_alpha`` (fp32) are [B, K]."""
+    what = "neighbor_join"
+    _req_dims(what, B=B, G=G, K=K, rank=rank)
+    _req_buf(what, all_img_ids, torch.int64, G, "all_image_tile_ids")
+    _req_buf(what, all_txt_ids, torch.int64, G, "all_text_tile_ids")
+    _req_buf(what, nbr_ids, torch.int64, B * K, "neighbor_tile_ids")
+    _req_buf(what, nbr_alpha, torch.float32, B * K, "neighbor_alphas")
+    _req_labels(what, lab_col, lab_w, B, K + 1)
     check(_lib.lib().sc_neighbor_join(all_img_ids.data_ptr(), all_txt_ids.data_ptr(), nbr_ids.data_ptr(),
                                       nbr_alpha.data_ptr(), B, G, K, rank, float(alpha_scale), lab_col.data_ptr(),
                                       lab_w.data_ptr(), _stream()), "sc_neighbor_join")
 
 
 def onehot_labels(B, rank, lab_col, lab_w):
+    _req_dims("onehot_labels", B=B, rank=rank)
+    _req_labels("onehot_labels", lab_col, lab_w, B, 1)
     check(_lib.lib().sc_onehot_labels(B, rank, lab_col.data_ptr(), lab_w.data_ptr(), _stream()), "sc_onehot_labels")
 
 
 def contrastive_loss_fwd(z, B, G, scale, cap, bias, lab_col, lab_w, nlab, w, rowstats, loss_out):
+    """ClipLoss / SpatialLoss rows pass + finalize on z [2, B, G]: rowstats [2B, 4], loss_out [4] (all fp32, contiguous)."""
+    what = "contrastive_loss_fwd"
+    _req_dims(what, B=B, G=G, nlab=nlab)
+    _req_buf(what, z, torch.float32, 2 * B * G, "z")
+    _req_scalar(what, scale, "logit_scale"); _req_scalar(what, bias, "logit_bias", optional=True)
+    _req_labels(what, lab_col, lab_w, B, nlab)
+    _req_buf(what, rowstats, torch.float32, 8 * B, "rowstats")
+    _req_buf(what, loss_out, torch.float32, 4, "loss_out")
     check(_lib.lib().sc_contrastive_loss_fwd(z.data_ptr(), B, G, scale.data_ptr(), float(cap), _ptr(bias),
                                              lab_col.data_ptr(), lab_w.data_ptr(), nlab, float(w),
                                              rowstats.data_ptr(), loss_out.data_ptr(), _stream()),
@@ -666,6 +713,18 @@ def contrastive_loss_fwd(z, B, G, scale, cap, bias, lab_col, lab_w, nlab, w, row
 
 def contrastive_loss_bwd(z, B, G, scale, cap, bias, lab_col, lab_w, nlab, w, rowstats, loss_out, grad_out, rowgrad,
                          dscale, dbias):
+    """Backward of ``contrastive_loss_fwd``: z <- dz in place, rowgrad [2B, 2], d_scale / d_bias (optional one-element slots);
+    ``grad_out``: the upstream gradient as a one-element device tensor, or None for 1."""
+    what = "contrastive_loss_bwd"
+    _req_dims(what, B=B, G=G, nlab=nlab)
+    _req_buf(what, z, torch.float32, 2 * B * G, "z")
+    _req_scalar(what, scale, "logit_scale"); _req_scalar(what, bias, "logit_bias", optional=True)
+    _req_scalar(what, grad_out, "grad_out", optional=True)
+    _req_labels(what, lab_col, lab_w, B, nlab)
+    _req_buf(what, rowstats, torch.float32, 8 * B, "rowstats")
+    _req_buf(what, loss_out, torch.float32, 4, "loss_out")
+    _req_buf(what, rowgrad, torch.float32, 4 * B, "rowgrad")
+    _req_scalar(what, dscale, "dscale", optional=True, exact=False); _req_scalar(what, dbias, "dbias", optional=True, exact=False)
     check(_lib.lib().sc_contrastive_loss_bwd(z.data_ptr(), B, G, scale.data_ptr(), float(cap), _ptr(bias),
                                              lab_col.data_ptr(), lab_w.data_ptr(), nlab, float(w),
                                              rowstats.data_ptr(), loss_out.data_ptr(), _ptr(grad_out),
@@ -674,6 +733,11 @@ def contrastive_loss_bwd(z, B, G, scale, cap, bias, lab_col, lab_w, nlab, w, row
 
 
 def recall_hits(z_img_rows, G, B, col0, hits3):
+    """R@1/5/10 hit counters (int32 [3], added onto) of B rows of row stride G whose diagonal block starts at column col0."""
+    what = "recall_hits"
+    _req_dims(what, G=G, B=B, col0=col0)
+    _req_buf(what, z_img_rows, torch.float32, max(B - 1, 0) * G + col0 + B, "z_image_rows")
+    _req_buf(what, hits3, torch.int32, 3, "hits3")
     check(_lib.lib().sc_recall_hits(z_img_rows.data_ptr(), G, B, col0, hits3.data_ptr(), _stream()), "sc_recall_hits")
 
 
@@ -717,6 +781,17 @@ def group_cache_put(image_features, text_features, image_cache, text_cache, j: i
 
 
 def siglip_loss(z, B, G, col0, scale, bias, rowpart, loss_out, dscale, dbias, hits3=None):
+    """SigLIP rows pass + finalize: z [B, G] <- dz in place, rowpart [B, 3]; loss_out / dscale / dbias: optional one-element
+    slots; ``hits3``: optional int32 [3] recall counters, read from z before it is overwritten."""
+    what = "siglip_loss"
+    _req_dims(what, B=B, G=G, col0=col0)
+    _req_buf(what, z, torch.float32, B * G, "z")
+    _req_scalar(what, scale, "logit_scale"); _req_scalar(what, bias, "logit_bias", optional=True)
+    _req_buf(what, rowpart, torch.float32, 3 * B, "rowpart")
+    for t_, n in ((loss_out, "loss_out"), (dscale, "dscale"), (dbias, "dbias")):
+        _req_scalar(what, t_, n, optional=True, exact=False)
+    if hits3 is not None:
+        _req_buf(what, hits3, torch.int32, 3, "hits3")
     check(_lib.lib().sc_siglip_loss(z.data_ptr(), B, G, col0, scale.data_ptr(), _ptr(bias), rowpart.data_ptr(),
                                     _ptr(loss_out), _ptr(dscale), _ptr(dbias), _ptr(hits3), _stream()),
           "sc_siglip_loss")
