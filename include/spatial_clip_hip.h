@@ -356,6 +356,20 @@ int sc_contrastive_loss_bwd(float* z_inout, int B, int G, const float* logit_sca
                             const float* grad_out, float* rowgrad, float* dscale, float* dbias, void* stream);
 /* RecallAtK (src/models/components/metrics.py:22-36) on the local [B,B] block of z[0]: hits3 += {R@1,R@5,R@10}. */
 int sc_recall_hits(const float* z_image_rows, int G, int B, int col0, int* hits3, void* stream);
+/* Full-set retrieval ranks (get_clip_metrics, src/open_clip_train/train.py:383-400) without the N x N matrix.
+ * z_ij = dot(image_feat row i, text_feat row j) in fp32 on the f32 MFMA, d_i = z_ii, for the rows i of the block
+ * [row0, row0 + M) against all N columns (image_feat / text_feat [N][D] fp32, row strides ld_image / ld_text >= D):
+ *   rank_i2t[i - row0]  = #{ j != i          : z_ij > d_i or (z_ij == d_i and j < i) }     [M] ints, WRITTEN
+ *   cnt_t2i[j]         += #{ i in block, != j : z_ij > d_j or (z_ij == d_j and i < j) }     [N] ints, ADDED ONTO
+ * i.e. sc_recall_hits' tie rule: the 0-based position of the ground truth under a stable descending sort.  Row blocks
+ * that partition [0, N), accumulated into one cleared cnt_t2i, leave the text->image rank of every column.  z_ij is one
+ * function of (row i, row j) whatever the block, tile position, stride or alignment, and the diagonals come from it: two
+ * bit-identical rows tie exactly.  A diagonal that is not finite is ranked last: rank_i2t = N - 1, and every row of a
+ * block counts against such a column, N - 1 over a partition.  z is never stored; the only writes are the two integer
+ * vectors (rank_i2t cleared on the stream, then integer atomics: bit-identical from launch to launch).  N, D >= 1,
+ * 0 <= row0, M >= 0 (0: nothing is launched), row0 + M <= N; otherwise an error and nothing launched. */
+int sc_retrieval_ranks(const float* image_feat, long long ld_image, const float* text_feat, long long ld_text, int N,
+                       int D, int row0, int M, int* rank_i2t, int* cnt_t2i, void* stream);
 /* Group cache of cached-feature gradient accumulation (Trainer accum_freq = N; open_clip --accum-freq): ONE launch copies what
  * micro-batch j leaves for the group's loss into row block j -- rows [j*B, (j+1)*B) -- of the contiguous caches
  * image_cache / text_cache [N*B][D] (fp32), image_id_cache / text_id_cache [N*B] (int64), neighbor_id_cache [N*B][K] (int64)

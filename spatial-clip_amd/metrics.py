@@ -9,7 +9,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import comm, ops
+from . import comm, ops      # ops binds the kernel library on first call, not on import: retrieval_summary needs no device
 
 
 class ContrastiveMetrics:
@@ -53,6 +53,105 @@ class ContrastiveMetrics:
         if self.hits is not None:
             self.hits.zero_()
         self.total = 0
+
+
+def check_retrieval_ks(ks) -> tuple:
+    ks = tuple(ks)
+    if not ks or any(isinstance(k, bool) or not isinstance(k, int) or k < 1 for k in ks):
+        raise ValueError(f"full_retrieval: ks must be a non-empty sequence of positive ints, got {ks!r}")
+    return ks
+
+
+def retrieval_summary(rank_i2t, rank_t2i, ks=(1, 5, 10), prefix: str = "") -> Dict[str, float]:
+    """Host half of :class:`RetrievalMetrics`, pure numpy: the quantities of the reference's ``get_clip_metrics``
+    (src/open_clip_train/train.py:391-398) under its names, from the 0-based ranks of the ground truth in each direction:
+    ``{dir}_mean_rank`` = mean + 1, ``{dir}_median_rank`` = floor(median) + 1, ``{dir}_R@k`` = mean(rank < k) for
+    dir in image_to_text, text_to_image, plus ``retrieval_num_samples``."""
+    ks = check_retrieval_ks(ks)
+    r_i = np.asarray(rank_i2t).astype(np.int64).reshape(-1)
+    r_t = np.asarray(rank_t2i).astype(np.int64).reshape(-1)
+    if r_i.shape != r_t.shape:
+        raise ValueError(f"retrieval_summary: {r_i.shape[0]} image->text ranks vs {r_t.shape[0]} text->image ranks")
+    out: Dict[str, float] = {}
+    for name, r in (("image_to_text", r_i), ("text_to_image", r_t)):
+        if r.size == 0:
+            vals = [float("nan")] * (2 + len(ks))
+        else:
+            vals = [float(r.mean() + 1), float(np.floor(np.median(r)) + 1)] + [float(np.mean(r < k)) for k in ks]
+        out[f"{prefix}{name}_mean_rank"], out[f"{prefix}{name}_median_rank"] = vals[0], vals[1]
+        for k, v in zip(ks, vals[2:]):
+            out[f"{prefix}{name}_R@{k}"] = v
+    out[f"{prefix}retrieval_num_samples"] = float(r_i.size)
+    return out
+
+
+class RetrievalMetrics:
+    """Full-set retrieval metrics: image->text and text->image mean rank, median rank and R@k over ALL pairs fed since the
+    last ``reset()`` -- open_clip's ``get_clip_metrics`` (src/open_clip_train/train.py:383-400), independent of the batch
+    size, where :class:`ContrastiveMetrics` ranks a positive among the columns of its own batch only.
+
+    ``update`` appends the fp32 feature rows to two device buffers that grow geometrically (no host sync); ``compute``
+    launches ``ops.retrieval_ranks`` once over everything (the N x N similarities are never stored: 2 N D floats of
+    features + 2 N ints) and copies the two int32 rank vectors to the host, the only synchronisation.  Memory: a buffer
+    doubles when full, so up to twice the stored rows stay allocated per side, and while one side grows its old and its new
+    buffer are both alive (three times the stored rows of that side, for the length of one copy).  ``reset()`` keeps the
+    buffers: only the first pass over a split grows them.
+
+    Deviations from the reference: ranks are taken on the raw cosines, not on ``logit_scale * cosine`` -- a positive scale
+    preserves the order except where its rounding makes or breaks a tie; and ties have a defined order (the stable
+    descending sort: equal scores rank by index) where the reference's ``argsort`` leaves it open.  A pair whose own
+    similarity is not finite is ranked last."""
+
+    def __init__(self, prefix: str, ks=(1, 5, 10)):
+        self.prefix = prefix
+        self.ks = check_retrieval_ks(ks)
+        self.image = None          # [capacity, D] fp32 each
+        self.text = None
+        self.n = 0
+
+    def _grow(self, need: int, D: int, device) -> None:
+        cap = 0 if self.image is None else self.image.shape[0]
+        if self.image is not None and self.image.shape[1] != D:
+            raise ValueError(f"RetrievalMetrics: feature width changed from {self.image.shape[1]} to {D}")
+        if need <= cap:
+            return
+        new_cap = max(need, 2 * cap, 1024)
+        for name in ("image", "text"):
+            buf = torch.empty((new_cap, D), dtype=torch.float32, device=device)
+            if self.n:
+                buf[:self.n].copy_(getattr(self, name)[:self.n])
+            setattr(self, name, buf)
+
+    def update(self, image_features: torch.Tensor, text_features: torch.Tensor) -> None:
+        if comm.is_dist():
+            raise ValueError("full_retrieval (RetrievalMetrics) is single-process for now: under a process group the "
+                             "validation features would have to be gathered and the text->image counts all-reduced")
+        if image_features.dim() != 2 or image_features.shape != text_features.shape:
+            raise ValueError(f"RetrievalMetrics: expected two [B, D] feature matrices, got {tuple(image_features.shape)} "
+                             f"and {tuple(text_features.shape)}")
+        B, D = image_features.shape
+        if B == 0:
+            return
+        self._grow(self.n + B, D, image_features.device)
+        self.image[self.n:self.n + B].copy_(image_features.detach())
+        self.text[self.n:self.n + B].copy_(text_features.detach())
+        self.n += B
+
+    __call__ = update
+
+    def ranks(self):
+        """(rank_i2t, rank_t2i): device int32 [n] each, one kernel launch, no host sync."""
+        return ops.retrieval_ranks(self.image[:self.n], self.text[:self.n])
+
+    def compute(self) -> Dict[str, float]:
+        if self.n == 0:
+            return retrieval_summary([], [], self.ks, self.prefix)
+        r_i, r_t = self.ranks()
+        both = torch.stack([r_i, r_t]).cpu().numpy()
+        return retrieval_summary(both[0], both[1], self.ks, self.prefix)
+
+    def reset(self) -> None:
+        self.n = 0
 
 
 class ZeroShotGeneExpressionMetric:

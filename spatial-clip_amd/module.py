@@ -10,12 +10,13 @@ import functools
 import inspect
 import operator
 import os
+from collections.abc import Mapping
 from typing import Any, Callable, Dict, Optional
 
 import torch
 
 from . import comm, ops
-from .metrics import ContrastiveMetrics, ZeroShotGeneExpressionMetric
+from .metrics import ContrastiveMetrics, RetrievalMetrics, ZeroShotGeneExpressionMetric, check_retrieval_ks
 from .net import SpatialClipNet
 
 
@@ -93,12 +94,31 @@ def check_teacher_config(student, teacher) -> None:
         diff("text vocab_size", student.text.vocab_size, teacher.text.vocab_size)
 
 
+def check_full_retrieval_cfg(cfg) -> Optional[tuple]:
+    """``full_retrieval`` of the module -> the ks of its RetrievalMetrics, or None when the feature is off."""
+    if cfg is None or cfg is False:
+        return None
+    if cfg is True:
+        return RetrievalMetrics("").ks
+    if isinstance(cfg, Mapping):
+        unknown = sorted(set(cfg) - {"ks"})
+        if unknown:
+            raise ValueError(f"full_retrieval: unknown key(s) {unknown}; the mapping form is {{'ks': [...]}}")
+        return check_retrieval_ks(cfg["ks"]) if cfg.get("ks") is not None else RetrievalMetrics("").ks
+    raise ValueError(f"full_retrieval must be None, a bool or a mapping {{'ks': [...]}}, got {type(cfg).__name__}: {cfg!r}")
+
+
 class SpatialClipLitModule(torch.nn.Module):
     def __init__(self, net: SpatialClipNet, loss_fn: torch.nn.Module, optimizer_cfg: Callable, scheduler_cfg: Callable,
                  train_metrics: Optional[ContrastiveMetrics] = None, val_metrics: Optional[ContrastiveMetrics] = None,
                  test_metrics: Optional[ContrastiveMetrics] = None, global_hvg_path: Optional[str] = None,
-                 dist_net: Optional[SpatialClipNet] = None, param_groups: Any = None):
+                 dist_net: Optional[SpatialClipNet] = None, param_groups: Any = None, full_retrieval: Any = None):
         super().__init__()
+        # full-set retrieval metrics of validation / test (config key model.full_retrieval; open_clip's get_clip_metrics):
+        # None / False -- off, nothing is allocated or launched; True or {"ks": [...]} -- one RetrievalMetrics per prefix
+        ks = check_full_retrieval_cfg(full_retrieval)
+        self.val_retrieval = RetrievalMetrics("val/", ks) if ks else None
+        self.test_retrieval = RetrievalMetrics("test/", ks) if ks else None
         # optimiser parameter groups (config key model.param_groups): None -- the reference's un-grouped
         # optimizer_cfg(params=self.parameters()); a mapping {"no_decay": "open_clip" | None, "lr_scale": {prefix: factor}};
         # or a callable (net) -> list of group dicts.  Checked here, so that a bad key fails before anything trains.
@@ -405,6 +425,8 @@ class SpatialClipLitModule(torch.nn.Module):
         self.log("val/loss", output["loss"], on_step=False, on_epoch=True, prog_bar=True, sync_dist=True)
         self._log_terms("val/", on_step=False, on_epoch=True, sync_dist=True)
         self.log_dict(self.val_metrics, on_step=False, on_epoch=True, sync_dist=True)
+        if self.val_retrieval is not None:
+            self.val_retrieval.update(output["image_features"], output["text_features"])
         self._zero_shot_update(batch, output, "val/zero_shot_pcc")
 
     def test_step(self, batch: Dict[str, Any], batch_idx: int) -> None:
@@ -413,6 +435,8 @@ class SpatialClipLitModule(torch.nn.Module):
         self.log("test/loss", output["loss"], on_step=False, on_epoch=True, sync_dist=True)
         self._log_terms("test/", on_step=False, on_epoch=True, sync_dist=True)
         self.log_dict(self.test_metrics, on_step=False, on_epoch=True, sync_dist=True)
+        if self.test_retrieval is not None:
+            self.test_retrieval.update(output["image_features"], output["text_features"])
         self._zero_shot_update(batch, output, "test/zero_shot_pcc")
 
     def optimizer_param_groups(self):

@@ -741,6 +741,38 @@ def recall_hits(z_img_rows, G, B, col0, hits3):
     check(_lib.lib().sc_recall_hits(z_img_rows.data_ptr(), G, B, col0, hits3.data_ptr(), _stream()), "sc_recall_hits")
 
 
+def retrieval_ranks(image_feat, text_feat, row0: int = 0, M: Optional[int] = None, rank_i2t=None, cnt_t2i=None):
+    """Full-set retrieval ranks of the pairs (image_feat[i], text_feat[i]), both fp32 [N, D] with any row stride >= D
+    (``sc_retrieval_ranks``; the N x N similarities are never stored).  For the rows i of [row0, row0 + M) (M None: up to N)
+    against all N columns, with z_ij = <image_i, text_j> and d_i = z_ii:
+    ``rank_i2t`` (int32 [M], written) = #{j != i: z_ij > d_i or (z_ij == d_i and j < i)}; ``cnt_t2i`` (int32 [N], ADDED onto;
+    a zeroed one is made when None) += #{i in block, i != j: z_ij > d_j or (z_ij == d_j and i < j)}: summed over row blocks
+    that partition [0, N) it is the text->image rank.  Returns ``(rank_i2t, cnt_t2i)``."""
+    what = "retrieval_ranks"
+    _req(image_feat, torch.float32, "image_feat"); _req(text_feat, torch.float32, "text_feat")
+    if image_feat.dim() != 2 or text_feat.shape != image_feat.shape or image_feat.shape[0] < 1 or image_feat.shape[1] < 1:
+        raise ValueError(f"{what}: image_feat and text_feat must be [N, D] of one shape with N, D >= 1, got "
+                         f"{tuple(image_feat.shape)} and {tuple(text_feat.shape)}")
+    N, D = image_feat.shape
+    for t_, n in ((image_feat, "image_feat"), (text_feat, "text_feat")):
+        if N > 1 and t_.stride(0) < D:
+            raise ValueError(f"{what}: {n} rows overlap (row stride {t_.stride(0)} < D = {D})")
+    if M is None:
+        M = N - row0
+    _req_dims(what, row0=row0, M=M)
+    if rank_i2t is None:
+        rank_i2t = torch.empty(M, dtype=torch.int32, device=image_feat.device)
+    if cnt_t2i is None:
+        cnt_t2i = torch.zeros(N, dtype=torch.int32, device=image_feat.device)
+    _req_buf(what, rank_i2t, torch.int32, M, "rank_i2t")
+    _req_buf(what, cnt_t2i, torch.int32, N, "cnt_t2i")
+    ld_i = image_feat.stride(0) if N > 1 else D
+    ld_t = text_feat.stride(0) if N > 1 else D
+    check(_lib.lib().sc_retrieval_ranks(image_feat.data_ptr(), ld_i, text_feat.data_ptr(), ld_t, N, D, row0, M,
+                                        rank_i2t.data_ptr(), cnt_t2i.data_ptr(), _stream()), "sc_retrieval_ranks")
+    return rank_i2t, cnt_t2i
+
+
 def group_cache_put(image_features, text_features, image_cache, text_cache, j: int, N: int, image_tile_ids=None,
                     text_tile_ids=None, neighbor_tile_ids=None, neighbor_alphas=None, image_id_cache=None, text_id_cache=None,
                     neighbor_id_cache=None, neighbor_alpha_cache=None) -> None:

@@ -246,6 +246,9 @@ class Trainer:
         val = datamodule.val_dataloader()
         n_val = self._limit(len(val), self.limit_val_batches)
         model.val_metrics.reset()
+        full = getattr(model, "val_retrieval", None)         # full-set retrieval metrics (model.full_retrieval), else None
+        if full is not None:
+            full.reset()
         model.on_validation_start()
         if model.zero_shot_metric:
             model.zero_shot_metric.reset()
@@ -258,6 +261,8 @@ class Trainer:
         if vl:
             out["val/loss"] = self._synced(model, "val/loss", float(torch.stack(vl).mean()))
             out.update(model.val_metrics.compute())
+            if full is not None:
+                out.update(full.compute())
             if model.zero_shot_metric and model.gene_bank_embeddings is not None:
                 out["val/zero_shot_pcc"] = model.zero_shot_metric.compute()
         return out
@@ -560,6 +565,9 @@ class Trainer:
         loader = datamodule.test_dataloader()
         n = self._limit(len(loader), self.limit_test_batches)
         model.test_metrics.reset()
+        full = getattr(model, "test_retrieval", None)
+        if full is not None:
+            full.reset()
         tl = []
         for i, batch in enumerate(loader):
             if i >= n:
@@ -567,6 +575,6 @@ class Trainer:
             model.test_step(_to_device(batch, model.device), i)
             tl.append(model.logged["test/loss"])
         out = {"test/loss": self._synced(model, "test/loss", float(torch.stack(tl).mean())),
-               **model.test_metrics.compute()} if tl else {}
+               **model.test_metrics.compute(), **(full.compute() if full is not None else {})} if tl else {}
         self.callback_metrics = {**self.callback_metrics, **{k: v for k, v in out.items() if isinstance(v, float)}}
         return [out]
