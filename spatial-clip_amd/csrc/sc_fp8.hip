@@ -222,10 +222,9 @@ static int gemm_fp8_impl(int epi, const void* A8, int lda, const float* a_scale_
     const bool f32out = (epi == SC_EPI_F32 || epi == SC_EPI_F32_BIAS_RES);
     SC_CHECK(!sc_epi_aux_mul(epi) || (aux != nullptr && (ldaux % 8) == 0), "sc_gemm_fp8: the GELU' epilogues need aux (ldaux %% 8 == 0)");
     SC_CHECK((N % (f32out ? 4 : 8)) == 0 && (ldc % 4) == 0 && ((uintptr_t)C % 16) == 0, "sc_gemm_fp8: N=%d ldc=%d", N, ldc);
-    GemmArgs g;
-    g.A = (const bf16*)A8; g.B = (const bf16*)B8; g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2;
-    g.C = C; g.ldc = ldc; g.C2 = C2; g.ldc2 = ldc2; g.bias = bias; g.res = (const float*)res; g.ldres = ldres;
-    g.aux = (const bf16*)aux; g.ldaux = ldaux; g.colsum = nullptr; g.tile_offset = 0;
+    GemmArgs g = sc_gemm_args(A8, lda / 2, B8, ldb / 2, M, N, K / 2, C, ldc);      // K / lda / ldb in 2-byte units
+    g.C2 = C2; g.ldc2 = ldc2; g.bias = bias; g.res = (const float*)res; g.ldres = ldres;
+    g.aux = (const bf16*)aux; g.ldaux = ldaux;
     g.a_scale = a_scale_inv; g.b_scale = b_scale_inv; g.a_scale_scalar = a_scale_scalar;
     g.act = act;
     if (q8_out != nullptr) {
@@ -234,8 +233,9 @@ static int gemm_fp8_impl(int epi, const void* A8, int lda, const float* a_scale_
                  "sc_gemm_fp8_q: q8 output needs its scale, 64 amax slots and an 8-byte aligned row stride (ldq8=%lld)", ldq8);
         g.q8 = (unsigned char*)q8_out; g.ldq8 = ldq8; g.q8_scale = q8_scale; g.q8_amax = q8_amax;
     }
-    const int took = sc_gemm8p_fp8(epi, g, (hipStream_t)stream);
-    SC_CHECK(took == 1, "sc_gemm_fp8: shape not supported (M=%d N=%d K=%d epi=%d)", M, N, K, epi);
+    if (epi == SC_EPI_GELU_GRAD_PAIR && sc_gemm_lut_wanted()) g.gelu_lut = sc_gelu_lut_device((hipStream_t)stream, act);
+    if (const int rc = sc_gemm8p_fp8_launch(epi, g, (hipStream_t)stream)) return rc;
+    sc_gemm_note_path(SC_GEMM_PATH_FP8_NT, g.gelu_lut != nullptr, 0, 1, SC_GEMM_COLSUM_NONE);
     return 0;
 }
 

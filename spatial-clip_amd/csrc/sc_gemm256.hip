@@ -9,7 +9,6 @@
 // (ragged K, tiny problems).  Edges in M/N are handled by clamping the source row/column (the duplicated
 // results are never stored); K (per split) must be a multiple of 64.
 #include "sc_gemm_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -221,75 +220,23 @@ int launch1(const GemmArgs& g, int nblocks, hipStream_t st) {
     }
     gemm256_kernel<MODE, EPI, NI><<<nblocks, 512, LDS_BYTES, st>>>(g);
     SC_LAUNCH_CHECK();
-    return 1;
+    return 0;
 }
 
-// full rounds with whole tiles, then the remainder cut into halves / quarters so that it still covers the chip
+// whole tiles, then the partial last round cut into halves / quarters where the plan asks for it (SC_GEMM_TAIL=1:
+// plan_256, sc_gemm_dispatch.hip)
 template <int MODE, int EPI>
-int launch(GemmArgs& g, int ntiles, hipStream_t st) {
-    constexpr int CUS = 256;
-    // measured (interleaved A/B on one MI355X, ViT-B/16 step): splitting the last round is 0.4 ms/step SLOWER than
-    // leaving it whole -- workgroups are not in lockstep rounds, the hardware backfills; opt-in only (SC_GEMM_TAIL=1)
-    static const bool tail_split = (getenv("SC_GEMM_TAIL") && getenv("SC_GEMM_TAIL")[0] == '1');
-    const int rem = ntiles % CUS;
-    int msplit = 1;
-    if (tail_split && g.splitk == 1 && g.colsum == nullptr && ntiles > CUS && rem > 0) {
-        if (rem * 4 <= CUS) msplit = 4;
-        else if (rem * 2 <= CUS + 64) msplit = 2;
-    }
-    g.tile_offset = 0;
-    if (msplit == 1) return launch1<MODE, EPI, 8>(g, ntiles, st);
-    const int nfull = ntiles - rem;
-    int rc = launch1<MODE, EPI, 8>(g, nfull, st);
-    if (rc != 1) return rc;
-    g.tile_offset = nfull;
-    return msplit == 4 ? launch1<MODE, EPI, 2>(g, rem * 4, st) : launch1<MODE, EPI, 4>(g, rem * 2, st);
+int launch(const GemmPlan& p, GemmArgs g, hipStream_t st) {
+    static_assert(LDS_BYTES == SC_GEMM256_LDS, "the planner's LDS figure");
+    if (p.tail_parts == 0) return launch1<MODE, EPI, 8>(g, p.tiles, st);
+    if (const int rc = launch1<MODE, EPI, 8>(g, p.tail_first, st)) return rc;
+    g.tile_offset = p.tail_first;
+    return p.tail_parts == 4 ? launch1<MODE, EPI, 2>(g, p.tail_rem * 4, st) : launch1<MODE, EPI, 4>(g, p.tail_rem * 2, st);
 }
 
 }  // namespace
 
-int sc_gemm256_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, float* c_final, hipStream_t st) {
-    // eligibility: enough work for 256-tiles, K a multiple of 64 per split, inner dims allow clamped 16-byte chunks
-    if (g.M < 256 || g.N < 192 || (g.K % BK) != 0) return 0;
-    if (mode == SC_GEMM_TN && ((g.M % 8) != 0 || (g.N % 8) != 0)) return 0;
-    const long long work = (long long)g.M * g.N;
-    if (work < 256LL * 256 * 8) return 0;
-    if (mode == SC_GEMM_NT && splitk_req <= 1) {      // few tiles: the 128x128 general kernel (see sc_gemm8p_try)
-        static const int small_tiles = getenv("SC_GEMM_SMALL_TILES") ? atoi(getenv("SC_GEMM_SMALL_TILES")) : 100;
-        if (work < 256LL * 256 * small_tiles) return 0;
-    }
-    g.ntm = (g.M + BM - 1) / BM;
-    g.ntn = (g.N + BN - 1) / BN;
-    const int ktiles = g.K / BK;
-    int splitk = splitk_req < 1 ? 1 : splitk_req;
-    if (epi != SC_EPI_F32 || slabs == nullptr) splitk = 1;
-    if (splitk > ktiles) splitk = ktiles;
-    int tiles_per = (ktiles + splitk - 1) / splitk;
-    splitk = (ktiles + tiles_per - 1) / tiles_per;
-    g.splitk = splitk;
-    g.k_per_split = tiles_per * BK;
-    g.slab_stride = 0;
-    if (splitk > 1) {
-        if (g.ldc != g.N) return 0;
-        g.C = slabs;
-        g.slab_stride = (long long)g.M * g.N;
-    }
-    const int nblocks = g.ntm * g.ntn * splitk;
-    sc_gemm_note_path(mode == SC_GEMM_NT ? SC_GEMM_PATH_NT256 : SC_GEMM_PATH_TN256, 0, 0, splitk,
-                      g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
-    int rc = 0;
-#define SC_CASE(MODE, EPI) \
-    if (mode == MODE && epi == EPI) rc = launch<MODE, EPI>(g, nblocks, st);
-    SC_CASE(SC_GEMM_NT, SC_EPI_BF16)
-    SC_CASE(SC_GEMM_NT, SC_EPI_BF16_BIAS)
-    SC_CASE(SC_GEMM_NT, SC_EPI_F32_BIAS_RES)
-    SC_CASE(SC_GEMM_NT, SC_EPI_GELU_PAIR)
-    SC_CASE(SC_GEMM_NT, SC_EPI_BF16_DGELU)
-    SC_CASE(SC_GEMM_NT, SC_EPI_BF16_BIAS_RES)
-    SC_CASE(SC_GEMM_NT, SC_EPI_GELU_GRAD_PAIR)
-    SC_CASE(SC_GEMM_NT, SC_EPI_BF16_MUL_AUX)
-    SC_CASE(SC_GEMM_NT, SC_EPI_F32)
-    SC_CASE(SC_GEMM_TN, SC_EPI_F32)
-#undef SC_CASE
-    return rc;
+int sc_gemm256_launch(int mode, int epi, const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+    return sc_mode_epi_dispatch<SC_EPI_F32>(
+        mode, epi, [&](auto MODE, auto EPI) { return launch<decltype(MODE)::value, decltype(EPI)::value>(p, g, st); });
 }

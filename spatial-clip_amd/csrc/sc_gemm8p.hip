@@ -28,9 +28,8 @@
 //
 //   Tail split (non-persistent kernel, splitk == 1): the tiles of a launch's partial last round run as HALF TILES of 128 rows
 //   (half_tile below: two phases and three images per K tile, nine-slot ring -- the same two rules, derived there), one per
-//   CU, so the round costs a half tile's time.  Which launches: sc_debug_gemm_tail_rule / sc_tail_default at the launcher.
+//   CU, so the round costs a half tile's time.  Which launches: tail_rule / plan_nt8p in sc_gemm_dispatch.hip.
 #include "sc_gemm_common.h"
-#include <stdlib.h>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -672,7 +671,7 @@ SC_DEVICE void half_tile(const GemmArgs& g, char* smem, int mh, int n0) {
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // Tail split (sc_gemm8p_try): workgroups [0, tail_first) compute the first tail_first tiles of the walk as full tiles, XCD
+    // Tail split (plan_nt8p, sc_gemm_dispatch.hip): workgroups [0, tail_first) compute the first tail_first tiles of the walk as full tiles, XCD
     // remap over those alone; the last 2 tail_rem workgroups compute the remaining tail_rem tiles as half tiles.  Their own
     // XCD remap gives an XCD a contiguous run of (tile, half) pairs, so the two halves of a tile share their B panel in one L2.
     int idx, hh = -1;
@@ -1314,8 +1313,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_f8_kernel(const GemmArgs g) {
     }
 }
 
-// Host side.  Launch of one of this file's 512-thread kernels with `lds` bytes of dynamic LDS; the kernel's limit (lds_max) is
-// raised on its first launch, once per kernel: Kernel is a template argument, so every kernel has its own flag.
+// Launch of one of this file's 512-thread kernels with `lds` bytes of dynamic LDS; the kernel's limit (lds_max) is raised on its
+// first launch, once per kernel: Kernel is a template argument, so every kernel has its own flag.
 template <auto Kernel, class... Args>
 int launch_lds(int grid, int lds_max, int lds, hipStream_t st, const Args&... args) {
     static bool attr_done = false;
@@ -1325,89 +1324,30 @@ int launch_lds(int grid, int lds_max, int lds, hipStream_t st, const Args&... ar
     }
     Kernel<<<grid, 512, lds, st>>>(args...);
     SC_LAUNCH_CHECK();
-    return 1;
-}
-
-// f(std::integral_constant<int, EPI>) for the run-time epilogue `epi`; 0 when there is no such epilogue
-template <class F>
-int epi_dispatch(int epi, F f) {
-#define SC_CASE(EPI) \
-    if (epi == EPI) return f(std::integral_constant<int, EPI>{});
-    SC_CASE(SC_EPI_BF16)
-    SC_CASE(SC_EPI_BF16_BIAS)
-    SC_CASE(SC_EPI_F32_BIAS_RES)
-    SC_CASE(SC_EPI_GELU_PAIR)
-    SC_CASE(SC_EPI_BF16_DGELU)
-    SC_CASE(SC_EPI_F32)
-    SC_CASE(SC_EPI_BF16_BIAS_RES)
-    SC_CASE(SC_EPI_GELU_GRAD_PAIR)
-    SC_CASE(SC_EPI_BF16_MUL_AUX)
-#undef SC_CASE
     return 0;
 }
 
-// Split-K plan: `req` slices (one without slabs to reduce through) over ktiles K tiles, evened out so that no slice is empty.
-// Returns the slice count; *tiles_per = K tiles per slice.
-int splitk_plan(int ktiles, int req, bool has_slabs, int* tiles_per) {
-    int splitk = (req < 1 || !has_slabs) ? 1 : req;
-    if (splitk > ktiles) splitk = ktiles;
-    *tiles_per = (ktiles + splitk - 1) / splitk;
-    return (ktiles + *tiles_per - 1) / *tiles_per;
-}
-// The plan for K tiles of bk, written into g; with more than one slice the output goes to the slabs.  false = split-K asked
-// of an output that is not dense (ldc != N)
-bool splitk_set(GemmArgs& g, int bk, int req, float* slabs, bool has_slabs) {
-    int tiles_per = 0;
-    g.splitk = splitk_plan(g.K / bk, req, has_slabs, &tiles_per);
-    g.k_per_split = tiles_per * bk;
-    g.slab_stride = 0;
-    if (g.splitk > 1) {
-        if (g.ldc != g.N) return false;
-        g.C = slabs;
-        g.slab_stride = (long long)g.M * g.N;
-    }
-    return true;
-}
+static_assert(LDS_BYTES == SC_GEMM256_LDS && HRING == SC_GEMM8P_HALF_LDS && HRING >= LDS_BYTES && RING + 8 * 4096 == SC_GEMM8PP_LDS,
+              "the planner's LDS figures; gemm8p_kernel's limit is raised once, to the half tiles' ring");
 
 }  // namespace
 
-// fp8 NT GEMM: g.A / g.B point at e4m3 bytes, g.K / lda / ldb already halved ("2-byte units"); 1 = launched
-int sc_gemm8p_fp8(int epi, GemmArgs& g, hipStream_t st) {
-    if (g.M < 1 || g.N < 8 || (g.K % BK) != 0) return 0;
-    g.ntm = (g.M + BM - 1) / BM;
-    g.ntn = (g.N + BN - 1) / BN;
-    g.splitk = 1;
-    g.k_per_split = g.K;
-    g.slab_stride = 0;
-    const int nblocks = g.ntm * g.ntn;
-    if (epi == SC_EPI_GELU_GRAD_PAIR) {
-        const char* sw = getenv("SC_GELU_LUT");
-        if (!(sw && sw[0] == '0')) g.gelu_lut = sc_gelu_lut_device(st, g.act);
+int sc_gemm8p_launch(int mode, int epi, const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+    if (mode == SC_GEMM_TN) return launch_lds<&gemm8p_tn_kernel>(p.grid, p.lds_max, p.lds, st, g);
+    if (p.path == SC_GEMM_PATH_NT8P_PERSISTENT) {
+        if (epi == SC_EPI_BF16) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16>>(p.grid, p.lds_max, p.lds, st, g, p.tiles);
+        if (epi == SC_EPI_BF16_BIAS) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16_BIAS>>(p.grid, p.lds_max, p.lds, st, g, p.tiles);
+        if (epi == SC_EPI_GELU_PAIR) return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_PAIR>>(p.grid, p.lds_max, p.lds, st, g, p.tiles);
+        return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_GRAD_PAIR>>(p.grid, p.lds_max, p.lds, st, g, p.tiles);
     }
-    sc_gemm_note_path(SC_GEMM_PATH_FP8_NT, g.gelu_lut != nullptr, 0, 1, SC_GEMM_COLSUM_NONE);
-    return epi_dispatch(epi, [&](auto E) {
-        return launch_lds<&gemm8p_f8_kernel<decltype(E)::value>>(nblocks, LDS_BYTES, LDS_BYTES, st, g);
+    return sc_epi_dispatch(epi, [&](auto E) {
+        return launch_lds<&gemm8p_kernel<decltype(E)::value>>(p.grid, p.lds_max, p.lds, st, g);
     });
 }
 
-// Grouped TN launch (sc_gemm_wgrad_group): every g[p] describes dW_p[M_p, N_p] = A_p[K, M_p]^T . B_p[K, N_p] with the SAME K;
-// C / slab_stride / colsum are set by the caller for the split-K factor returned by sc_gemm8p_tn_group_plan.
-// 1 = launched, 0 = some problem is outside the 256x256 kernel's range (the caller runs the problems one by one).
-int sc_gemm8p_tn_group_plan(const GemmArgs* g, int n, int splitk_req, int* splitk_out, int* k_per_split) {
-    if (n < 1 || n > SC_WGRAD_GROUP_MAX) return 0;
-    const int K = g[0].K;
-    if ((K % BK) != 0) return 0;
-    for (int p = 0; p < n; ++p) {
-        if (g[p].K != K || g[p].M < 256 || g[p].N < 192 || (g[p].M % 8) != 0 || (g[p].N % 8) != 0) return 0;
-        if ((long long)g[p].M * g[p].N < 256LL * 256 * 8 || g[p].ldc != g[p].N) return 0;
-    }
-    int tiles_per = 0;
-    *splitk_out = splitk_plan(K / BK, splitk_req, true, &tiles_per);
-    *k_per_split = tiles_per * BK;
-    return 1;
-}
+// every g[p] describes dW_p[M_p, N_p] = A_p[K, M_p]^T . B_p[K, N_p] with the SAME K and split-K
 int sc_gemm8p_tn_group_launch(const GemmArgs* g, int n, hipStream_t st) {
-    GemmGroup gg;
+    GemmGroup gg{};
     gg.n = n;
     int total = 0;
     for (int p = 0; p < n; ++p) {
@@ -1416,172 +1356,23 @@ int sc_gemm8p_tn_group_launch(const GemmArgs* g, int n, hipStream_t st) {
         total += g[p].ntm * g[p].ntn * g[p].splitk;
     }
     for (int p = n; p <= SC_WGRAD_GROUP_MAX; ++p) gg.first[p] = total;
-    bool sums = false;
-    for (int p = 0; p < n; ++p) sums = sums || g[p].colsum != nullptr;
-    sc_gemm_note_path(SC_GEMM_PATH_TN8P_GROUP, 0, 0, g[0].splitk, sums ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
-    sc_gemm_note_group(SC_GEMM_GROUP_ONE_LAUNCH);
     return launch_lds<&gemm8p_tn_group_kernel>(total, LDS_BYTES, LDS_BYTES, st, gg);
 }
 
-// fp8 TN weight gradient: g.A / g.B e4m3 bytes [K][M] / [K][N] (lda / ldb in bytes), g.a_scale / g.b_scale device scalars, g.C fp32;
-// split-K through `slabs` exactly as the bf16 TN path.  1 = launched, 0 = shape outside the kernel's range.
-int sc_gemm8p_tn_fp8(GemmArgs& g, int splitk_req, float* slabs, hipStream_t st) {
-    if (g.M < 256 || g.N < 192 || (g.K % 128) != 0 || (g.M % 16) != 0 || (g.N % 16) != 0) return 0;
-    if ((g.lda % 16) != 0 || (g.ldb % 16) != 0) return 0;
-    g.ntm = (g.M + BM - 1) / BM;
-    g.ntn = (g.N + BN - 1) / BN;
-    if (!splitk_set(g, 128, splitk_req, slabs, slabs != nullptr)) return 0;
-    sc_gemm_note_path(SC_GEMM_PATH_FP8_TN, 0, 0, g.splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
+int sc_gemm8p_tn_fp8_launch(const GemmArgs& g, hipStream_t st) {
     return launch_lds<&gemm8p_tn_f8_kernel>(g.ntm * g.ntn * g.splitk, LDS_BYTES, LDS_BYTES, st, g);
 }
 
-// Which launches take the column-group walk by default (measured per launch class: profiles/r05_gemm_colgroup.txt).
-static int sc_colgroup_default(int epi, const GemmArgs& g) {
-    (void)epi; (void)g;
-    return 0;
-}
-
-// Tail split of the non-persistent NT kernel.  T tiles on S workgroup slots (one 140-KiB workgroup per CU) run in ceil(T / S)
-// rounds, and the last one keeps only rem = T % S of the S CUs busy.  When rem <= S / 2 those rem tiles are launched as 2 rem
-// half tiles (128 rows each, dispatched last), one per CU: the last round then costs a half tile's time instead of a tile's.
-// With more than S / 2 tiles in the last round the halves would not all find a free CU at once; with T <= S there is one round.
-extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem) {
-    const int r = (S > 0 && T > S) ? T % S : 0;
-    const bool split = r > 0 && 2 * r <= S;
-    if (nfull) *nfull = split ? T - r : T;
-    if (rem) *rem = split ? r : 0;
-    return split ? 1 : 0;
-}
-
-// (nfull, rem) of the last launch of the non-persistent NT kernel by this process, (T, 0) when it was not split, (-1, -1) before
-// the first one or after a reset: host-side bookkeeping for tests (which kernel a shape reached, and whether its tail was split)
-static int sc_last_tail[2] = {-1, -1};
-extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset) {
-    if (nfull) *nfull = sc_last_tail[0];
-    if (rem) *rem = sc_last_tail[1];
-    if (reset) sc_last_tail[0] = sc_last_tail[1] = -1;
-    return 0;
-}
-
-// The kernel the last GEMM entry point dispatched to (enum sc_gemm_path and the fields of sc_debug_gemm_last_path,
-// sc_kernels.h): host-side bookkeeping for tests, like the record above.
-static int sc_last_path[6] = {SC_GEMM_PATH_NONE, 0, 0, 0, SC_GEMM_COLSUM_NONE, SC_GEMM_GROUP_NONE};
-void sc_gemm_note_path(int path, int lut, int col_group, int splitk, int colsum) {
-    sc_last_path[0] = path; sc_last_path[1] = lut; sc_last_path[2] = col_group; sc_last_path[3] = splitk;
-    sc_last_path[4] = colsum; sc_last_path[5] = SC_GEMM_GROUP_NONE;
-}
-void sc_gemm_note_colsum(int colsum) { sc_last_path[4] = colsum; }
-void sc_gemm_note_group(int group) { sc_last_path[5] = group; }
-extern "C" int sc_debug_gemm_last_path(int* out, int n, int reset) {
-    for (int i = 0; i < n && i < 6; ++i) out[i] = sc_last_path[i];
-    if (reset) sc_gemm_note_path(SC_GEMM_PATH_NONE, 0, 0, 0, SC_GEMM_COLSUM_NONE);
-    return 6;
-}
-
-// workgroup slots of the current device = its CU count (queried once per device)
-static int sc_gemm_slots() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = -1;
-        cus[dev] = n;
-    }
-    return cus[dev] > 0 ? cus[dev] : 0;
-}
-
-// Which launch classes take the tail split by default.  Measured per class on the step's shapes (M = 50 432, alone on the chip,
-// switch off -> on, profiles/gemm_tail_summary.txt): N = 768 (591 tiles, 2.31 rounds) plain K = 768 / 2304 / 3072 67.6 -> 61.2 /
-// 165.2 -> 153.4 / 213.7 -> 199.4 us, bf16 residual K = 768 / 3072 82.6 -> 72.0 / 237.2 -> 215.2, fp32 residual K = 768 117.2 ->
-// 108.8; N = 3072 (2 364 tiles, 9.23 rounds) act-pair 303.1 -> 295.9, x act' 278.8 -> 274.6.  Every class gains, the short-K ones
-// (where a half tile's fixed prologue and epilogue weigh most) the most in relative terms: none is excluded.
-static bool sc_tail_default(int epi, const GemmArgs& g) {
-    (void)epi; (void)g;
-    return true;
-}
-
-int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, hipStream_t st) {
-    if (g.M < 256 || g.N < 192 || (g.K % BK) != 0) return 0;
-    if (mode == SC_GEMM_TN && (epi != SC_EPI_F32 || (g.M % 8) != 0 || (g.N % 8) != 0)) return 0;
-    if ((long long)g.M * g.N < 256LL * 256 * 8) return 0;
-    // NT launches with fewer 256x256 tiles than ~0.4 of the chip's CUs go to the 128x128 general kernel: four times the
-    // workgroups, two of them per CU.  Measured (tools/bench_small_m.py, profiles/r06_small_m_kernel_choice.txt; the token
-    // counts of ViT-B-32 + CLIP text tower at the reference's batch 32): 20-84 tiles 1.08-1.52x faster on the small kernel,
-    // 150 tiles and more 1.1-1.5x faster here.  SC_GEMM_SMALL_TILES=<n> moves the threshold (0: never).
-    if (mode == SC_GEMM_NT && splitk_req <= 1) {
-        static const int small_tiles = getenv("SC_GEMM_SMALL_TILES") ? atoi(getenv("SC_GEMM_SMALL_TILES")) : 100;
-        if ((long long)g.M * g.N < 256LL * 256 * small_tiles) return 0;
-    }
+int sc_gemm8p_fp8_launch(int epi, GemmArgs g, hipStream_t st) {
     g.ntm = (g.M + BM - 1) / BM;
     g.ntn = (g.N + BN - 1) / BN;
-    const int ktiles = g.K / BK;
-    if (!splitk_set(g, BK, splitk_req, slabs, epi == SC_EPI_F32 && slabs != nullptr)) return 0;
-    const int splitk = g.splitk;
-    const int nblocks = g.ntm * g.ntn * splitk;
-    if (mode == SC_GEMM_TN) {
-        sc_gemm_note_path(SC_GEMM_PATH_TN8P, 0, 0, splitk, g.colsum ? SC_GEMM_COLSUM_FUSED : SC_GEMM_COLSUM_NONE);
-        return launch_lds<&gemm8p_tn_kernel>(nblocks, LDS_BYTES, LDS_BYTES, st, g);
-    }
-    // GELU by table: only the non-persistent kernel has LDS to spare for it (the persistent one fills all 160 KiB)
-    if (epi == SC_EPI_GELU_GRAD_PAIR) {
-        const char* sw = getenv("SC_GELU_LUT");                  // read per call: A/B switch
-        if (!(sw && sw[0] == '0')) g.gelu_lut = sc_gelu_lut_device(st, g.act);
-    }
-    // persistent walk of the tile list for the store-only bf16 epilogues once there is more than one round of tiles
-    static const bool persist = !(getenv("SC_GEMM_PERSIST") && getenv("SC_GEMM_PERSIST")[0] == '0');
-    if (g.gelu_lut == nullptr && persist && splitk == 1 && nblocks >= 1024 && ktiles >= 3) {      // >= 4 rounds of tiles (measured: +7 % at 7 rounds, -3 % at 2.3)
-        if (epi == SC_EPI_BF16 || epi == SC_EPI_BF16_BIAS || epi == SC_EPI_GELU_PAIR || epi == SC_EPI_GELU_GRAD_PAIR) {     // GELU pair: +1.5 % at 9.2 rounds
-            sc_gemm_note_path(SC_GEMM_PATH_NT8P_PERSISTENT, 0, 0, 1, SC_GEMM_COLSUM_NONE);
-            const int grid = nblocks < 256 ? nblocks : 256, lds = RING + 8 * 4096;
-            if (epi == SC_EPI_BF16) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16>>(grid, lds, lds, st, g, nblocks);
-            if (epi == SC_EPI_BF16_BIAS) return launch_lds<&gemm8pp_kernel<SC_EPI_BF16_BIAS>>(grid, lds, lds, st, g, nblocks);
-            if (epi == SC_EPI_GELU_PAIR) return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_PAIR>>(grid, lds, lds, st, g, nblocks);
-            return launch_lds<&gemm8pp_kernel<SC_EPI_GELU_GRAD_PAIR>>(grid, lds, lds, st, g, nblocks);
-        }
-    }
-    // Tile walk of the non-persistent kernel: SC_GEMM_COLGROUP="<epi>:<Gc>[,<epi>:<Gc>...]" (A/B switch, read per call)
-    // walks the named epilogues' launches in column groups of Gc tiles inside per-XCD row bands (sc_tile_colgroup).
-    g.col_group = 0;
-    if (splitk == 1 && g.ntn > 1) {
-        int gc = sc_colgroup_default(epi, g);
-        if (const char* sw = getenv("SC_GEMM_COLGROUP")) {
-            for (const char* p = sw; *p;) {
-                char* e = nullptr;
-                const long ep = strtol(p, &e, 10);
-                if (e == p || *e != ':') break;
-                const long v = strtol(e + 1, &e, 10);
-                if (ep == epi || ep == -1) gc = (int)v;
-                p = (*e == ',') ? e + 1 : e;
-                if (*e != ',') break;
-            }
-        }
-        if (gc > 0 && gc < g.ntn) {
-            g.col_group = gc;
-            g.band_rows = (g.ntm + 7) / 8;                       // an XCD's contiguous share of the remapped tile list
-        }
-    }
-    // Tail split: SC_GEMM_TAIL (A/B switch, read per call) unset = the rule with the device's CU count for the classes of
-    // sc_tail_default, 0 = off, <n> = the rule with S = n for every class (the result does not depend on S).
-    g.tail_first = g.tail_rem = 0;
-    int grid = nblocks;
-    if (splitk == 1) {
-        const char* sw = getenv("SC_GEMM_TAIL");
-        const int slots = sw ? atoi(sw) : (sc_tail_default(epi, g) ? sc_gemm_slots() : 0);
-        int nfull = 0, rem = 0;
-        if (slots > 0 && sc_debug_gemm_tail_rule(nblocks, slots, &nfull, &rem)) {
-            g.tail_first = nfull;
-            g.tail_rem = rem;
-            grid = nfull + 2 * rem;
-        }
-    }
-    sc_last_tail[0] = g.tail_first > 0 ? g.tail_first : nblocks;
-    sc_last_tail[1] = g.tail_rem;
-    sc_gemm_note_path(SC_GEMM_PATH_NT8P, g.gelu_lut != nullptr, g.col_group, splitk, SC_GEMM_COLSUM_NONE);
-    // a launch with half tiles needs their nine-slot ring
-    const int lds_max = LDS_BYTES > HRING ? LDS_BYTES : HRING;
-    const int lds = g.tail_first > 0 ? lds_max : LDS_BYTES;
-    return epi_dispatch(epi, [&](auto E) { return launch_lds<&gemm8p_kernel<decltype(E)::value>>(grid, lds_max, lds, st, g); });
+    g.splitk = 1;
+    g.k_per_split = g.K;
+    const int rc = (g.M < 1 || g.N < 8 || (g.K % BK) != 0) ? -1 : sc_epi_dispatch(epi, [&](auto E) {
+        return launch_lds<&gemm8p_f8_kernel<decltype(E)::value>>(g.ntm * g.ntn, LDS_BYTES, LDS_BYTES, st, g);
+    });
+    SC_CHECK(rc != -1, "sc_gemm_fp8: shape not supported (M=%d N=%d K=%d epi=%d)", g.M, g.N, 2 * g.K, epi);
+    return rc;
 }
 
 // device copy of the GELU table, one per device and activation, filled on first use by the formula itself (sc_gemm_common.h)

@@ -9,6 +9,7 @@
 #pragma once
 #include "sc_common.h"
 #include "sc_kernels.h"
+#include <type_traits>
 
 struct GemmArgs {
     const bf16* A;
@@ -52,7 +53,7 @@ struct GemmArgs {
     // group by column group (Gc column tiles: a B sub-panel that stays in the XCD's 4-MB L2 while the band's rows stream by)
     int col_group = 0;
     int band_rows = 0;
-    // tail split of gemm8p_kernel (sc_gemm8p_try): 0 = every workgroup computes a 256x256 tile; nfull > 0 = workgroups
+    // tail split of gemm8p_kernel (plan_nt8p, sc_gemm_dispatch.hip): 0 = every workgroup computes a 256x256 tile; nfull > 0 = workgroups
     // [0, nfull) compute the first nfull tiles of the walk, the 2 * tail_rem workgroups after them the remaining tail_rem
     // tiles as 128-row half tiles (the partial last round of tiles, spread over twice as many CUs)
     int tail_first = 0;
@@ -365,20 +366,77 @@ SC_DEVICE void sc_epilogue_store(const float* ep, EpiRegs<EPI>& e, int gm0, int 
     }
 }
 
-// The record behind sc_debug_gemm_last_path (sc_gemm8p.hip).  sc_gemm_note_path starts a new record (a launcher calls it once it
-// knows its kernel); the other two amend the record of the call in progress.
-void sc_gemm_note_path(int path, int lut, int col_group, int splitk, int colsum);
-void sc_gemm_note_colsum(int colsum);
-void sc_gemm_note_group(int group);
+// ---- host side.  sc_gemm_dispatch.hip plans every launch (GemmPlan) and holds the C entry points; each kernel file launches its
+// own families from a plan that already accepted the problem: 0 = launched, < 0 = error (never "not taken"). ----
+struct GemmPlan {
+    int path = SC_GEMM_PATH_NONE;      // enum sc_gemm_path; NONE: no kernel takes the problem, `refused` says why
+    const char* refused = nullptr;
+    int splitk = 1, k_per_split = 0, ntm = 0, ntn = 0;
+    int tiles = 0, grid = 0;           // tiles = ntm * ntn * splitk
+    int lds = 0, lds_max = 0;          // dynamic LDS bytes of this launch, and the most its kernel ever asks for
+    bool lut = false;                  // the GELU table is wanted (sc_gelu_lut_device)
+    int col_group = 0, band_rows = 0;  // GemmArgs::col_group / band_rows
+    int tail_first = 0, tail_rem = 0;  // the partial last round: GemmArgs::tail_first / tail_rem (gemm8p_kernel), or the tiles
+    int tail_parts = 0;                //   gemm256_kernel launches again as `tail_parts` (2 / 4) row slices each; 0 = no split
+    int colsum = SC_GEMM_COLSUM_NONE;  // enum sc_gemm_colsum
+};
+constexpr int SC_GEMM128_LDS = 4 * 64 * SC_EPI_LD * 4;        // dynamic LDS as the planner states it: each launcher asserts its own
+constexpr int SC_GEMM256_LDS = 8 * 64 * SC_EPI_LD * 4;        // gemm256_kernel, gemm8p_kernel and the TN / fp8 kernels beside it
+constexpr int SC_GEMM8P_HALF_LDS = 9 * 128 * 64 * 2;          // gemm8p_kernel with half tiles: their nine-slot ring
+constexpr int SC_GEMM8PP_LDS = 8 * 128 * 64 * 2 + 8 * 4096;   // gemm8pp_kernel: the ring and eight epilogue strips
 
-// 256x256 LDS-DMA kernel (sc_gemm256.hip): returns 1 if it took the problem, 0 if not eligible, <0 on error
-int sc_gemm256_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, float* c_final, hipStream_t st);
-// 256x256x64 phase-interleaved (ping-pong) kernel, NT only (sc_gemm8p.hip)
-int sc_gemm8p_try(int mode, int epi, GemmArgs& g, int splitk_req, float* slabs, hipStream_t st);
-// grouped TN launch of the same kernel (several weight gradients over one token axis): plan the common split-K, then launch
-int sc_gemm8p_tn_group_plan(const GemmArgs* g, int n, int splitk_req, int* splitk_out, int* k_per_split);
+// The operands of a problem; every other member is zero until the entry point or the plan sets it.
+inline GemmArgs sc_gemm_args(const void* A, long long lda, const void* B, long long ldb, int M, int N, int K, void* C, int ldc) {
+    GemmArgs g{};
+    g.A = (const bf16*)A; g.lda = (int)lda; g.B = (const bf16*)B; g.ldb = (int)ldb;
+    g.M = M; g.N = N; g.K = K; g.C = C; g.ldc = ldc;
+    return g;
+}
+
+// f(integral_constant<EPI>) for the run-time epilogue `epi`; -1 when there is no such epilogue
+template <class F>
+int sc_epi_dispatch(int epi, F f) {
+#define SC_CASE(EPI) \
+    if (epi == EPI) return f(std::integral_constant<int, EPI>{});
+    SC_CASE(SC_EPI_BF16)
+    SC_CASE(SC_EPI_BF16_BIAS)
+    SC_CASE(SC_EPI_F32_BIAS_RES)
+    SC_CASE(SC_EPI_GELU_PAIR)
+    SC_CASE(SC_EPI_BF16_DGELU)
+    SC_CASE(SC_EPI_F32)
+    SC_CASE(SC_EPI_BF16_BIAS_RES)
+    SC_CASE(SC_EPI_GELU_GRAD_PAIR)
+    SC_CASE(SC_EPI_BF16_MUL_AUX)
+#undef SC_CASE
+    return -1;
+}
+// f(integral_constant<MODE>, integral_constant<EPI>) for NT x every epilogue and TN x the listed ones only: a kernel template is
+// instantiated for exactly these pairs
+template <int... TN_EPIS, class F>
+int sc_mode_epi_dispatch(int mode, int epi, F f) {
+    if (mode == SC_GEMM_NT) return sc_epi_dispatch(epi, [&](auto E) { return f(std::integral_constant<int, SC_GEMM_NT>{}, E); });
+    int rc = -1;
+    ((epi == TN_EPIS ? void(rc = f(std::integral_constant<int, SC_GEMM_TN>{}, std::integral_constant<int, TN_EPIS>{})) : void()), ...);
+    return rc;
+}
+
+int sc_gemm128_launch(int mode, int epi, const GemmPlan& p, const GemmArgs& g, hipStream_t st);      // sc_gemm.hip
+int sc_gemm256_launch(int mode, int epi, const GemmPlan& p, const GemmArgs& g, hipStream_t st);      // sc_gemm256.hip
+// sc_gemm8p.hip: gemm8p_kernel / gemm8pp_kernel / gemm8p_tn_kernel by p.path; n TN problems of one K in one launch; the e4m3 TN
+// weight gradient (lda / ldb in bytes); the e4m3 NT kernel (g.K / lda / ldb in 2-byte units; it fills the tile counts itself)
+int sc_gemm8p_launch(int mode, int epi, const GemmPlan& p, const GemmArgs& g, hipStream_t st);
 int sc_gemm8p_tn_group_launch(const GemmArgs* g, int n, hipStream_t st);
-// fp8 (e4m3) TN weight gradient (per-tensor scales; lda / ldb in bytes); 1 = launched, 0 = shape outside its range
-int sc_gemm8p_tn_fp8(GemmArgs& g, int splitk_req, float* slabs, hipStream_t st);
-// fp8 (e4m3) NT variant of the same kernel; g.K / lda / ldb in 2-byte units, g.a_scale / g.b_scale set
-int sc_gemm8p_fp8(int epi, GemmArgs& g, hipStream_t st);
+int sc_gemm8p_tn_fp8_launch(const GemmArgs& g, hipStream_t st);
+int sc_gemm8p_fp8_launch(int epi, GemmArgs g, hipStream_t st);
+
+// Split-K slabs [nslab][M x N] -> out (slabs null: the GEMM wrote `out` itself) and partial column sums [nslab][M] -> cs_out
+// (null: none), summed in the order z = 0 .. nslab - 1; for one output, or n of them in one launch.  sc_gemm.hip
+struct ReduceOne {
+    float* out; const float* slabs; int M, N; float* cs_out; const float* cs_part;
+};
+int sc_reduce_slabs_launch(const ReduceOne& r, int nslab, hipStream_t st);
+int sc_reduce_slabs_group_launch(const ReduceOne* r, int n, int nslab, hipStream_t st);
+
+// sc_gemm_dispatch.hip: the GELU-table switch (SC_GELU_LUT, read per call) and the record behind sc_debug_gemm_last_path
+bool sc_gemm_lut_wanted();
+void sc_gemm_note_path(int path, int lut, int col_group, int splitk, int colsum);

@@ -17,7 +17,7 @@ enum sc_attn_path {
 // take under the current environment switches; -1 with sc_attn_fwd's own message for a shape they refuse.  No HIP call.
 extern "C" int sc_debug_attn_last_path(int* fwd, int* bwd);
 extern "C" int sc_debug_attn_plan(int B, int L, int H, int dh, int causal, int q_rows, int* fwd, int* bwd);
-// sc_debug_gemm_tail_rule: the tail-split rule of the 256x256 NT kernel for T tiles on S workgroup slots (sc_gemm8p.hip).  Returns 1
+// sc_debug_gemm_tail_rule: the tail-split rule of the 256x256 NT kernel for T tiles on S workgroup slots (sc_gemm_dispatch.hip).  Returns 1
 // and (nfull, rem) = (T - T % S, T % S) when the last round is split into 2 rem half tiles, else 0 and (T, 0).  Host arithmetic only.
 extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem);
 // sc_debug_gemm_last_tail: (nfull, rem) of this process's last launch of the non-persistent 256x256 NT kernel ((T, 0): not split;
@@ -25,7 +25,7 @@ extern "C" int sc_debug_gemm_tail_rule(int T, int S, int* nfull, int* rem);
 extern "C" int sc_debug_gemm_last_tail(int* nfull, int* rem, int reset);
 
 // Which kernel the last GEMM entry point of this process (sc_gemm_bf16, sc_gemm_wgrad_bias, sc_gemm_wgrad_group, sc_gemm_fp8*,
-// sc_gemm_wgrad_fp8) dispatched to.  Written by the launchers, host-side bookkeeping only (a few int stores per call); the
+// sc_gemm_wgrad_fp8) dispatched to.  Written by the entry points after the launch, host-side bookkeeping only (a few int stores per call); the
 // tests assert with it that a shape reached the kernel they are named for.
 enum sc_gemm_path {
     SC_GEMM_PATH_NONE = -1,
@@ -47,3 +47,9 @@ enum sc_gemm_group { SC_GEMM_GROUP_NONE = 0, SC_GEMM_GROUP_ONE_LAUNCH, SC_GEMM_G
 // actually used, sc_gemm_colsum, sc_gemm_group} of the last GEMM call (of the last problem, for a group that ran per problem);
 // path SC_GEMM_PATH_NONE before the first call or after a reset.  reset != 0 clears the record.  Returns the number of fields.
 extern "C" int sc_debug_gemm_last_path(int* out, int n, int reset);
+// sc_debug_gemm_plan: what sc_gemm_bf16 (colsum == 0) or sc_gemm_wgrad_bias (colsum != 0: TN, fp32 out) would launch for this problem
+// under the current environment switches on a device of `slots` CUs (<= 0: no tail split): out[0 .. n) = the six fields of
+// sc_debug_gemm_last_path, then (nfull, rem) of sc_debug_gemm_last_tail.  The planner the entry points call; no HIP call.  -1 with
+// the entry point's own message for a problem it refuses.
+extern "C" int sc_debug_gemm_plan(int mode, int epi, int M, int N, int K, int ldc, int splitk, int has_slabs, int colsum,
+                                  int slots, int* out, int n);

@@ -277,6 +277,22 @@ def gemm_last_path(reset: bool = False) -> GemmPath:
                     GEMM_GROUPS[out[5]])
 
 
+def gemm_plan(mode: int, epi: int, M: int, N: int, K: int, *, ldc: Optional[int] = None, splitk: int = 1,
+              has_slabs: bool = False, colsum: bool = False, slots: int = 0):
+    """(GemmPath, (nfull, rem)): what ``gemm_last_path`` / ``gemm_last_tail`` would report after ``gemm`` (``colsum``:
+    ``gemm_wgrad_bias``) of this problem under the current environment switches on a device of ``slots`` CUs (0: no tail
+    split), without launching anything (``sc_debug_gemm_plan``: the planner the entry points call, host arithmetic only, so
+    it runs without a GPU).  ``ldc`` defaults to a dense ``N``.  A problem the library refuses raises RuntimeError with the
+    entry point's own message."""
+    fn = getattr(_lib.lib(), "sc_debug_gemm_plan")
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    out = (ctypes.c_int * 8)()
+    check(fn(mode, epi, M, N, K, N if ldc is None else ldc, splitk, int(has_slabs), int(colsum), slots, out, 8),
+          "sc_debug_gemm_plan")
+    return (GemmPath(GEMM_PATHS[out[0]], bool(out[1]), out[2], out[3], GEMM_COLSUMS[out[4]], GEMM_GROUPS[out[5]]),
+            (out[6], out[7]))
+
+
 # ------------------------------------------------------------------------------------------ norms
 def _t8_args(t8, rows: int, d: int, what: str):
     """(buffer uint8 [rows, >= d], scale fp32 [1], amax fp32 [64]) -> ctypes arguments of a per-tensor e4m3 second output."""
